@@ -98,6 +98,25 @@ def cpu_baseline(env_id, batch, budget_s=12.0):
             "single_core": {"value": v_one, "cores": 1, "sample": s_one + ", one thread"}}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, outputs):
+    """DIR/<name>.npy (float32) for every output tensor of one step, rows = envs, plus env_index.npy (float64): the envs written.
+    All envs while they fit in DUMP_BUDGET_BYTES, else a sample of them fixed by a constant seed (the same one in every run
+    with the same batch)."""
+    import numpy as np
+    host = {k: v.cpu().numpy().astype(np.float32) for k, v in outputs.items()}
+    n = len(host["obs"])
+    per_env = sum(v[:1].nbytes for v in host.values()) + 8
+    m = min(n, (DUMP_BUDGET_BYTES - 4096 * (len(host) + 1)) // per_env)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "env_index.npy"), rows.astype(np.float64))
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v[rows]))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` as a plain command: start N fresh ranks through torch.distributed.run BEFORE anything in
     this process touches the GPU, relay their output (rank 0 prints the JSON line) and leave with their exit code."""
@@ -142,7 +161,12 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-host-path", action="store_true", help="skip the NumPy host-buffer path sample (sg_step, PCIe-inclusive)")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the one-launch-per-step chain")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (obs, reward, done, truncated of "
+                    "rank 0's envs, float32) to DIR/<name>.npy, a fixed seeded sample of the envs if they exceed 64 MB "
+                    "(bench_outputs/ inside the tree is git-ignored)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "RANK" not in os.environ and args.gpus > 1:
@@ -249,6 +273,12 @@ def main():
         run_steps(K)
         sync_all()
         repeats.append(time.perf_counter() - tr)
+    k_last = K - (K - 1) // chunk * chunk  # steps in the last chunk, whose outputs are still in the buffers
+    # ---- --dump-outputs: what the last timed step returned, copied before anything below reuses the rollout buffers
+    last_outputs = None
+    if args.dump_outputs:
+        last_outputs = {"obs": obs[k_last - 1].clone(), "reward": rew[k_last - 1].clone(),
+                        "done": done[k_last - 1].clone(), "truncated": trunc[k_last - 1].clone()}
 
     # ---- the same K steps again with start/stop events on every dispatch (hipExtLaunchKernelGGL): the kernel's own
     # duration, as rocprofv3 --kernel-trace reports it.  Straight after the timed regions, on the same clocks (after the
@@ -383,7 +413,6 @@ def main():
     red_dev = torch.device("cpu") if rehearse else dev
     dt_median = sorted(repeats)[len(repeats) // 2]
     stats = torch.tensor([dt, dt_unfused, dt_events or 0.0, gather_ms or 0.0, dt_median], device=red_dev, dtype=torch.float64)
-    k_last = K - (K - 1) // chunk * chunk  # steps in the last chunk, whose outputs are still in the buffers
     n_done = (done[:k_last].sum(dtype=torch.float64) * (K / k_last)).reshape(1).to(red_dev)
     ranks_info = None
     if world > 1:
@@ -469,6 +498,8 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.env, B, args.cpu_seconds)
         print(json.dumps(out), flush=True)
+        if last_outputs is not None:
+            dump_outputs(args.dump_outputs, last_outputs)
     env.close()
     if world > 1:
         dist.destroy_process_group()

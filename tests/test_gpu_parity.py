@@ -652,6 +652,30 @@ def test_bench_line_contract():
     assert c["single_core"]["cores"] == 1 and 0 < c["single_core"]["value"] <= c["value"] * 1.5
 
 
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's (obs, reward, done, truncated) of every env; two runs with the same
+    arguments write the same arrays (the timed steps span several rollout calls here: --chunk below --steps)"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, dumps = 4096, []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "4", "--preroll", "16",
+                              "--chunk", "16", "--repeats", "2", "--batch", str(B), "--no-cpu-baseline", "--no-host-path",
+                              "--no-graph", "--dump-outputs", d], capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 40
+        dumps.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("obs", "reward", "done", "truncated", "env_index")})
+    a, b = dumps
+    assert np.array_equal(a["env_index"], np.arange(B)) and a["obs"].shape == (B, 15)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert np.isfinite(a["obs"]).all() and np.isfinite(a["reward"]).all()
+    assert (np.abs(a["obs"][:, 2] ** 2 + a["obs"][:, 3] ** 2 - 1) < 1e-5).all()  # (cos, sin) of the ship's angle
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and set(np.unique(a["truncated"])) <= {0.0, 1.0}
+
+
 @pytest.mark.parametrize("name", ["goal_a", "goal_b", "goal_c", "kepler_a", "kepler_b", "kepler_c", "kepler_d"])
 def test_constructor_kwargs_match_reference_golden(name):
     """sg_create_ex / make_vec(env_id, **kwargs): the reference's constructor kwargs (goal.py:18-31, kepler.py:189-203) beyond

@@ -82,6 +82,42 @@ def test_bench_spawns_its_own_ranks():
         assert (out.stdout + out.stderr).count("bench.py needs an MI355X") == 2, (out.stdout + out.stderr)[-2000:]
 
 
+def test_bench_dump_outputs_files(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 file per output with one row per env written, env_index.npy (float64) naming those
+    envs; above the byte budget a sample of them, the same one every time, within the budget."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, D = 1000, 15
+    g = torch.Generator().manual_seed(0)
+    outputs = {"obs": torch.rand((B, D), generator=g), "reward": torch.rand(B, generator=g),
+               "done": (torch.rand(B, generator=g) < 0.1).to(torch.uint8), "truncated": torch.zeros(B, dtype=torch.uint8)}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    bench.dump_outputs(str(tmp_path / "all"), outputs)
+    full = load(tmp_path / "all")
+    assert sorted(full) == ["done", "env_index", "obs", "reward", "truncated"]
+    assert full["env_index"].dtype == np.float64 and np.array_equal(full["env_index"], np.arange(B))
+    for k, v in outputs.items():
+        assert full[k].dtype == np.float32 and np.array_equal(full[k], v.numpy().astype(np.float32)), k
+
+    budget = 100 * (4 * (D + 3) + 8) + 4096 * 5
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    bench.dump_outputs(str(tmp_path / "a"), outputs)
+    bench.dump_outputs(str(tmp_path / "b"), outputs)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= budget
+    rows = a["env_index"].astype(np.int64)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and rows[-1] < B
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        if k != "env_index":
+            assert np.array_equal(a[k], full[k][rows]), k
+
+
 def test_no_vector_register_spills_in_the_default_kernels():
     """The wave-pair kernels are compiled for two waves per SIMD (256 vector registers) and sit close to that limit: a few
     registers more and the compiler spills to scratch inside the step loops (measured: +40 % per step).  The compiler's

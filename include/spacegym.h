@@ -14,7 +14,7 @@
  *   - no allocation, no host synchronisation and no host<->device copy inside the *_device calls:
  *     they only enqueue kernels on the given stream (hipGraph-capturable);
  *   - the host-buffer calls (sg_reset, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
- *     sg_seed, sg_set_auto_reset) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
+ *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
  *     the caller's streams before, and return when they are complete -- no manual synchronisation between the two kinds;
  *   - a handle is not thread-safe; independent handles are.
  *   - observations/rewards are float32 (the reference returns float64; parity tolerance in DESIGN.md).
@@ -199,6 +199,52 @@ typedef struct sg_counters {
 int sg_set_counters(sg_env *env, int32_t on);                              /* switching (on or off) zeroes the counters */
 int sg_get_counters(sg_env *env, sg_counters *out, int32_t reset);         /* waits for the enqueued work first */
 
+/* Episode statistics -- what gym.wrappers.RecordEpisodeStatistics (SB3 VecMonitor, info["episode"]) adds around a bare
+ * SpaceshipEnv, which keeps none itself: per env the return (float64 sum of the step rewards since the episode began, added in
+ * step order, one add per step: bit-identical to a float64 loop over the float32 rewards the calls return) and the length (steps
+ * in the episode); both start again from zero after every step with done (a terminal event or a truncation; with auto_reset
+ * off as well: every done row closes exactly one episode).  Off by default: nothing is allocated or launched for it then.  On,
+ * the handle keeps the two running sums per env on the device (12 B per env; sg_reset / sg_reset_device and switching on or
+ * off zero them, sg_set_state leaves them alone), and every stepping call -- sg_step, sg_step_device, sg_step_begin,
+ * sg_rollout_device, sg_rollout_device_terminal and the *_episodes calls below -- is followed, on the same stream, by a pass
+ * over the reward / done / truncated rows it wrote.  Calls that return no statistics still advance the sums (the episodes they
+ * finish are dropped), so the sums never depend on which entry point stepped the env.  Captured graphs stay linear (one stream).
+ * The *_episodes entry points fail with SG_ERR_INVALID while the statistics are off.  Switching them on or off invalidates the
+ * pointers sg_step_end returned (the result blocks grow by the two rows) and is refused while a step is in flight. */
+int sg_set_episode_stats(sg_env *env, int32_t on);
+/* sg_step_device / sg_step plus the episodes finished in this step, as dense rows like terminal_obs: ep_return float64
+ * [num_envs] and ep_length int32 [num_envs]; rows of envs with done receive the finished episode's return and length, other rows
+ * are left untouched.  Device pointers (on hip_stream) / host pointers. */
+int sg_step_device_episodes(sg_env *env, const void *actions_dev, float *obs_dev, float *reward_dev, uint8_t *done_dev,
+                            uint8_t *truncated_dev, float *terminal_obs_dev, double *ep_return_dev, int32_t *ep_length_dev,
+                            void *hip_stream);
+int sg_step_episodes(sg_env *env, const void *actions_host, float *obs_host, float *reward_host, uint8_t *done_host,
+                     uint8_t *truncated_host, float *terminal_obs_host, double *ep_return_host, int32_t *ep_length_host);
+/* With statistics on, the result block of sg_step_begin also carries the two rows (12 B per env more); sg_step_end_episodes
+ * returns pointers to them for the step sg_step_end collected last, valid under the same rules as sg_step_end's: ep_return
+ * float64 [num_envs], ep_length int32 [num_envs]; rows of envs that did not finish read NaN / -1. */
+int sg_step_end_episodes(sg_env *env, const double **ep_return, const int32_t **ep_length);
+/* The finished episodes of a rollout, one record per env-step with done, appended in no particular order (device memory, owned
+ * by the caller), as sg_terminal_list:
+ *   count      uint32 [1]            records appended by this call (set to 0 first); keeps counting past `capacity`, the excess
+ *                                    records are dropped
+ *   step_env   int32  [capacity, 2]  (step within this call, env index)
+ *   ret        float64 [capacity]    the episode's return
+ *   length     int32  [capacity]     its length
+ *   truncated  uint8  [capacity]     1 if it ended by the time limit ("TimeLimit.truncated") */
+typedef struct sg_episode_list {
+    uint32_t *count;
+    int32_t *step_env;
+    double *ret;
+    int32_t *length;
+    uint8_t *truncated;
+    uint32_t capacity;
+} sg_episode_list;
+/* sg_rollout_device (terminal == NULL) / sg_rollout_device_terminal plus the list of the episodes it finished. */
+int sg_rollout_device_episodes(sg_env *env, int32_t n_steps, const void *actions_dev, float *obs_dev, float *reward_dev,
+                               uint8_t *done_dev, uint8_t *truncated_dev, const sg_terminal_list *terminal,
+                               const sg_episode_list *episodes, void *hip_stream);
+
 /* On-device action source for sg_rollout_device: the uniformly random policy (what the reference's README loop and the
  * benchmark use: env.action_space.sample(), gym spaces Box / Discrete).  Fills actions_dev [n_steps, num_envs, 2] float32
  * with i.i.d. U(-1, 1) values (discrete ids: int32 [n_steps, num_envs] uniform in 0..5).  Entry (t, i) is a function of
@@ -219,7 +265,9 @@ int sg_set_state(sg_env *env, const float *ship, const float *planets, const flo
  * per-env column -- ship, planets, goal / orbit, step and episode counters, and the tiling state HexagonalTiling keeps
  * between goal hits (hexagonal_tiling.py:99-128: free-tile list, ship / goal tile, column shifts) -- plus the RNG key.
  * Loading it into a handle of the same env id and batch size makes the following steps bit-identical to those that
- * followed the save. */
+ * followed the save.  While episode statistics are on the blob also carries the running return and length of every env
+ * (sg_state_bytes grows by 12 B per env; with them off it is what it was before they existed); loading such a blob switches
+ * the statistics on and resumes them bit-identically, loading one without them into a handle that has them on zeroes them. */
 size_t sg_state_bytes(const sg_env *env);
 int sg_save_state(sg_env *env, void *blob_host, size_t bytes);
 int sg_load_state(sg_env *env, const void *blob_host, size_t bytes);

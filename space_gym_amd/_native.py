@@ -29,6 +29,11 @@ class SgTerminalList(C.Structure):
     _fields_ = [("count", C.c_void_p), ("step_env", C.c_void_p), ("obs", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class SgEpisodeList(C.Structure):
+    _fields_ = [("count", C.c_void_p), ("step_env", C.c_void_p), ("ret", C.c_void_p), ("length", C.c_void_p),
+                ("truncated", C.c_void_p), ("capacity", C.c_uint32)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -63,6 +68,12 @@ SYMBOLS = {
     "sg_rollout_device": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_set_unfused_rollout": (C.c_int, [_vp, C.c_int32]),
     "sg_rollout_device_terminal": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp]),
+    "sg_set_episode_stats": (C.c_int, [_vp, C.c_int32]),
+    "sg_step_device_episodes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_step_episodes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_step_end_episodes": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "sg_rollout_device_episodes": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList),
+                                             C.POINTER(SgEpisodeList), _vp]),
     "sg_check_status": (C.c_int, [_vp]),
     "sg_set_counters": (C.c_int, [_vp, C.c_int32]),
     "sg_get_counters": (C.c_int, [_vp, C.POINTER(SgCounters), C.c_int32]),

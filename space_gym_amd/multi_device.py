@@ -21,7 +21,8 @@ from .vector_env import SpaceGymVectorEnv, _ENGINE_KWARGS
 class MultiDeviceVectorEnv:
     def __init__(self, env_id, num_envs, devices, seed=0, env_index_base=0, copy=True, **kwargs):
         """devices: GPU indices, one block of envs each (the first is the root: where actions are taken from and results
-        land); an index may repeat (several blocks on one GPU: how the tests run it on a one-GPU box).  kwargs: make_vec's."""
+        land); an index may repeat (several blocks on one GPU: how the tests run it on a one-GPU box).  kwargs: make_vec's,
+        except episode_statistics: the per-device blocks do not gather episode statistics yet."""
         import torch
         self._torch = torch
         self.devices = [int(d) for d in devices]
@@ -34,6 +35,8 @@ class MultiDeviceVectorEnv:
         if kwargs:
             engine["env_kwargs"] = {**(engine.get("env_kwargs") or {}), **kwargs}
         engine.pop("device", None)
+        if engine.pop("episode_statistics", False):
+            raise NotImplementedError("episode_statistics: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device has them)")
         engine.setdefault("terminal_observation", False)
         # a template block gives the native config and parameter block (and validates the keywords); sg_create_sharded_ex
         # then makes the real handles: contiguous blocks, env_index_base of block k = env_index_base + its first env

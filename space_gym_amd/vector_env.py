@@ -13,6 +13,10 @@ Two I/O modes:
     is in flight;
   * torch (`reset_torch`, `step_torch`, `rollout_torch`): device tensors in/out through sg_step_device on torch's
     current stream, zero-copy -- the high-throughput path.
+
+Episode statistics (`episode_statistics=True` / `set_episode_statistics`): the return and length of every finished episode,
+with gym.wrappers.RecordEpisodeStatistics' semantics, summed on the device by a pass behind every stepping call --
+`info["episode"]` / `info["_episode"]` of step(), `episodes=` of step_torch and rollout_torch.
 """
 import ctypes as C
 
@@ -25,7 +29,9 @@ from .spaces import MultiDiscrete, batch_box
 
 
 class StepInfo(dict):
-    """Batched info: {"TimeLimit.truncated": bool[B], "terminal_observation": float32[B, D] (rows of finished envs)}.
+    """Batched info: {"TimeLimit.truncated": bool[B], "terminal_observation": float32[B, D] (rows of finished envs)}; with
+    episode statistics on also "episode": {"r": float64[B], "l": int32[B]} and the mask "_episode": bool[B] of the envs whose
+    episode ended (gymnasium's vector convention; other rows of "r" / "l" read NaN / -1).
     A per-env list of dicts (old gym VectorEnv) would cost more than the step itself at B = 65536."""
 
 
@@ -34,7 +40,7 @@ class SpaceGymVectorEnv:
 
     def __init__(self, env_id, num_envs, device=0, seed=0, env_index_base=0, max_episode_steps=None, auto_reset=True,
                  validate_actions=True, terminal_observation=True, copy=True, steering=None, env_kwargs=None, from_class=False,
-                 _handle=None):
+                 episode_statistics=False, _handle=None):
         """steering: "velocity" (ship_steering=1, what every registered id uses) or "acceleration" (ship_steering=0, the
         constructor default of the reference classes: omega is a state, the thruster a torque); None: what env_kwargs say.
         env_kwargs: keyword arguments of the reference's constructor (GoalEnv.__init__ goal.py:18-31, KeplerEnv.__init__
@@ -45,7 +51,8 @@ class SpaceGymVectorEnv:
         (spaceship_env.py:71; discrete ids: ValueError, :201-202); off, out-of-range actions are clamped on the device (the
         device-tensor calls never validate: that would need a device-to-host synchronisation).
         copy=False: reset()/step() return views of the engine's pinned output buffers, overwritten by the next call
-        (no per-step allocation or copy); copy=True returns fresh arrays like gym's vector envs."""
+        (no per-step allocation or copy); copy=True returns fresh arrays like gym's vector envs.
+        episode_statistics: switch the episode statistics on from the start (set_episode_statistics)."""
         if env_id not in ENV_SPECS:
             raise ValueError(f"unknown env id {env_id!r}; served ids: {sorted(ENV_SPECS)}")
         self._lib = _native.load()
@@ -91,6 +98,9 @@ class SpaceGymVectorEnv:
         self._pending = False
         self._blocks = {}
         self._torch_bufs = None
+        self._episode_stats = False
+        if episode_statistics:
+            self.set_episode_statistics(True)
 
     def _native_params(self, kw):
         """sg_params (include/spacegym.h) from the constructor's keyword arguments"""
@@ -158,6 +168,23 @@ class SpaceGymVectorEnv:
         self._ck(self._lib.sg_get_counters(self._h, C.byref(k), int(bool(reset))), "sg_get_counters")
         return {f: int(getattr(k, f)) for f, _ in k._fields_}
 
+    def set_episode_statistics(self, on=True):
+        """gym.wrappers.RecordEpisodeStatistics on the device (sg_set_episode_stats): per env the float64 sum of the rewards and
+        the number of steps since the episode began, both reset by done.  Switching (on or off) zeroes them; off by default."""
+        if self._pending:
+            raise RuntimeError("set_episode_statistics() while a step is in flight (step_wait() first)")
+        self._ck(self._lib.sg_set_episode_stats(self._h, int(bool(on))), "sg_set_episode_stats")
+        self._episode_stats = bool(on)
+        self._blocks = {}  # the result blocks are made again with (or without) the two rows
+
+    @property
+    def episode_statistics(self):
+        return self._episode_stats
+
+    def _need_episode_stats(self, what):
+        if not self._episode_stats:
+            raise ValueError(f"{what}: episode statistics are off (make_vec(..., episode_statistics=True) or set_episode_statistics())")
+
     def set_auto_reset(self, on):
         self._ck(self._lib.sg_set_auto_reset(self._h, int(bool(on))), "sg_set_auto_reset")
 
@@ -208,6 +235,17 @@ class SpaceGymVectorEnv:
                                  view(ptrs[3], (B,), np.uint8), view(ptrs[4], (B, D), np.float32) if ptrs[4] else None)
         return self._blocks[key]
 
+    def _episode_views(self):
+        """NumPy views of the episode rows of the block sg_step_end returned last (sg_step_end_episodes)"""
+        r, l = C.c_void_p(), C.c_void_p()
+        self._ck(self._lib.sg_step_end_episodes(self._h, C.byref(r), C.byref(l)), "sg_step_end_episodes")
+        key = ("episode", r.value)
+        if key not in self._blocks:
+            B = self.num_envs
+            self._blocks[key] = (np.frombuffer((C.c_char * (8 * B)).from_address(r.value), dtype=np.float64),
+                                 np.frombuffer((C.c_char * (4 * B)).from_address(l.value), dtype=np.int32))
+        return self._blocks[key]
+
     def step_wait(self):
         if not self._pending:
             raise RuntimeError("step_wait() without step_async()")
@@ -219,6 +257,10 @@ class SpaceGymVectorEnv:
         info = StepInfo({"TimeLimit.truncated": trunc.view(np.bool_) if not self.copy else trunc.astype(bool)})
         if tobs is not None:
             info["terminal_observation"] = tobs.copy() if self.copy else tobs
+        if self._episode_stats:
+            r, l = self._episode_views()
+            info["episode"] = {"r": r.copy(), "l": l.copy()} if self.copy else {"r": r, "l": l}
+            info["_episode"] = done.astype(bool) if self.copy else done.view(np.bool_)
         if self.copy:
             return obs.copy(), rew.copy(), done.astype(bool), info
         return obs, rew, done.view(np.bool_), info
@@ -285,11 +327,13 @@ class SpaceGymVectorEnv:
         self._ck(self._lib.sg_reset_device(self._h, C.c_void_p(obs.data_ptr()), self._stream()), "sg_reset_device")
         return obs
 
-    def step_torch(self, actions, out=None, terminal_obs=None):
+    def step_torch(self, actions, out=None, terminal_obs=None, episodes=None):
         """actions: float32 CUDA tensor [B, 2] (discrete ids: int32 [B]), or any device array exporting DLPack
         (`__dlpack__`: CuPy, JAX, ...; taken zero-copy).  Returns (obs, reward, done, truncated) device tensors, which are
         reused by the next call unless `out` (a dict with the same keys) is given; `torch.utils.dlpack.to_dlpack` /
-        `__dlpack__` hands them on to other frameworks without a copy."""
+        `__dlpack__` hands them on to other frameworks without a copy.
+        episodes: dict(r=float64 [B], l=int32 [B]) of device tensors (episode statistics on): rows of envs that finished in
+        this step receive the return and length of the episode that ended, other rows are left untouched."""
         torch, bufs = self._torch()
         o = bufs if out is None else out
         if not isinstance(actions, torch.Tensor) and hasattr(actions, "__dlpack__"):
@@ -303,11 +347,17 @@ class SpaceGymVectorEnv:
             self._check_tensor("out['trunc']", o["trunc"], torch.uint8, (B,))
         if terminal_obs is not None:
             self._check_tensor("terminal_obs", terminal_obs, torch.float32, (B, D))
-        rc = self._lib.sg_step_device(self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(o["obs"].data_ptr()),
-                                      C.c_void_p(o["reward"].data_ptr()), C.c_void_p(o["done"].data_ptr()),
-                                      C.c_void_p(o["trunc"].data_ptr()),
-                                      C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None, self._stream())
-        self._ck(rc, "sg_step_device")
+        args = (self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(o["obs"].data_ptr()), C.c_void_p(o["reward"].data_ptr()),
+                C.c_void_p(o["done"].data_ptr()), C.c_void_p(o["trunc"].data_ptr()),
+                C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None)
+        if episodes is None:
+            self._ck(self._lib.sg_step_device(*args, self._stream()), "sg_step_device")
+        else:
+            self._need_episode_stats("step_torch(episodes=...)")
+            self._check_tensor("episodes['r']", episodes["r"], torch.float64, (B,))
+            self._check_tensor("episodes['l']", episodes["l"], torch.int32, (B,))
+            self._ck(self._lib.sg_step_device_episodes(*args, C.c_void_p(episodes["r"].data_ptr()), C.c_void_p(episodes["l"].data_ptr()),
+                                                       self._stream()), "sg_step_device_episodes")
         return o["obs"], o["reward"], o["done"], o["trunc"]
 
     def _check_tensor(self, name, t, dtype, shape):
@@ -319,11 +369,13 @@ class SpaceGymVectorEnv:
             raise ValueError(f"{name}: expected contiguous {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}"
                              f"{'' if t.is_contiguous() else ' (not contiguous)'}")
 
-    def rollout_torch(self, actions, obs, reward, done, trunc, terminal=None):
+    def rollout_torch(self, actions, obs, reward, done, trunc, terminal=None, episodes=None):
         """actions [K, B, 2] (discrete ids: int32 [K, B]) -> obs [K, B, D], reward/done/trunc [K, B]: K steps, one launch.
         terminal: optional dict(count=uint32/int32 [1], step_env=int32 [cap, 2], obs=float32 [cap, D]) of device tensors
         that receives one record per finished env-step: its (step, env) and the LAST observation of the episode that ended
-        there (sg_rollout_device_terminal); `terminal_records` turns it into sorted host arrays."""
+        there (sg_rollout_device_terminal); `terminal_records` turns it into sorted host arrays.
+        episodes: optional list from episode_list_torch (episode statistics on) that receives one record per finished episode:
+        (step, env), return, length, truncated (sg_rollout_device_episodes); `episode_records` sorts it."""
         import torch
         K, B, D = int(actions.shape[0]), self.num_envs, self.obs_dim
         self._check_tensor("actions", actions, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
@@ -333,22 +385,43 @@ class SpaceGymVectorEnv:
         self._check_tensor("trunc", trunc, torch.uint8, (K, B))
         args = (self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(reward.data_ptr()),
                 C.c_void_p(done.data_ptr()), C.c_void_p(trunc.data_ptr()))
-        if terminal is None:
-            self._ck(self._lib.sg_rollout_device(*args, self._stream()), "sg_rollout_device")
-        else:
+        el = self._episode_list_arg(episodes) if episodes is not None else None
+        tl = None
+        if terminal is not None:
             cap = int(terminal["step_env"].shape[0])
             if terminal["count"].dtype not in (torch.int32, torch.uint32) or terminal["count"].numel() != 1:
                 raise ValueError("terminal['count']: expected one 32-bit integer")
             self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
             self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, D))
             tl = _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap)
+        if el is not None:
+            self._ck(self._lib.sg_rollout_device_episodes(*args, C.byref(tl) if tl is not None else None, C.byref(el), self._stream()),
+                     "sg_rollout_device_episodes")
+        elif tl is None:
+            self._ck(self._lib.sg_rollout_device(*args, self._stream()), "sg_rollout_device")
+        else:
             self._ck(self._lib.sg_rollout_device_terminal(*args, C.byref(tl), self._stream()), "sg_rollout_device_terminal")
         return obs, reward, done, trunc
 
-    def prepare_rollout(self, actions, obs, reward, done, trunc):
+    def _episode_list_arg(self, episodes):
+        """SgEpisodeList over the tensors of an episode_list_torch() dict, checked"""
+        import torch
+        self._need_episode_stats("episodes=")
+        cap = int(episodes["step_env"].shape[0])
+        if episodes["count"].dtype not in (torch.int32, torch.uint32) or episodes["count"].numel() != 1:
+            raise ValueError("episodes['count']: expected one 32-bit integer")
+        self._check_tensor("episodes['count']", episodes["count"], episodes["count"].dtype, (1,))
+        self._check_tensor("episodes['step_env']", episodes["step_env"], torch.int32, (cap, 2))
+        self._check_tensor("episodes['r']", episodes["r"], torch.float64, (cap,))
+        self._check_tensor("episodes['l']", episodes["l"], torch.int32, (cap,))
+        self._check_tensor("episodes['truncated']", episodes["truncated"], torch.uint8, (cap,))
+        return _native.SgEpisodeList(episodes["count"].data_ptr(), episodes["step_env"].data_ptr(), episodes["r"].data_ptr(),
+                                     episodes["l"].data_ptr(), episodes["truncated"].data_ptr(), cap)
+
+    def prepare_rollout(self, actions, obs, reward, done, trunc, episodes=None):
         """Validates the buffers once and returns a zero-argument callable that enqueues the rollout on torch's current
         stream: for loops that re-use the same buffers (the per-call checks of rollout_torch cost more host time than a
-        short rollout takes on the GPU)."""
+        short rollout takes on the GPU).  episodes: as rollout_torch's."""
         import torch
         K, B, D = int(actions.shape[0]), self.num_envs, self.obs_dim
         self._check_tensor("actions", actions, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
@@ -356,13 +429,18 @@ class SpaceGymVectorEnv:
         self._check_tensor("reward", reward, torch.float32, (K, B))
         self._check_tensor("done", done, torch.uint8, (K, B))
         self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        el = self._episode_list_arg(episodes) if episodes is not None else None
         keep = (actions, obs, reward, done, trunc)  # the callable keeps the tensors alive
         args = (self._h, K) + tuple(C.c_void_p(t.data_ptr()) for t in keep)
-        fn, ck, dev = self._lib.sg_rollout_device, self._ck, self.device
+        fn, what, ck, dev = self._lib.sg_rollout_device, "sg_rollout_device", self._ck, self.device
+        if el is not None:
+            fn, what = self._lib.sg_rollout_device_episodes, "sg_rollout_device_episodes"
+            args += (None, C.byref(el))
+            keep += (episodes, el)
         cur = torch.cuda.current_stream
 
         def call():
-            ck(fn(*args, C.c_void_p(cur(dev).cuda_stream)), "sg_rollout_device")
+            ck(fn(*args, C.c_void_p(cur(dev).cuda_stream)), what)
         call.keep = keep
         return call
 
@@ -372,6 +450,28 @@ class SpaceGymVectorEnv:
         dev = torch.device("cuda", self.device)
         return dict(count=torch.zeros(1, dtype=torch.int32, device=dev), step_env=torch.empty((capacity, 2), dtype=torch.int32, device=dev),
                     obs=torch.empty((capacity, self.obs_dim), dtype=torch.float32, device=dev))
+
+    def episode_list_torch(self, capacity):
+        """device buffers for rollout_torch(..., episodes=...): count, step_env [cap, 2], r float64 [cap], l int32 [cap],
+        truncated uint8 [cap]"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        return dict(count=torch.zeros(1, dtype=torch.int32, device=dev), step_env=torch.empty((capacity, 2), dtype=torch.int32, device=dev),
+                    r=torch.empty(capacity, dtype=torch.float64, device=dev), l=torch.empty(capacity, dtype=torch.int32, device=dev),
+                    truncated=torch.empty(capacity, dtype=torch.uint8, device=dev))
+
+    @staticmethod
+    def episode_records(episodes):
+        """dict(step, env int32 [n], r float64 [n], l int32 [n], truncated bool [n]) sorted by (step, env); raises if the
+        list overflowed"""
+        n = int(episodes["count"].item())
+        cap = int(episodes["step_env"].shape[0])
+        if n > cap:
+            raise OverflowError(f"episode list overflow: {n} records, capacity {cap}")
+        se = episodes["step_env"][:n].cpu().numpy()
+        order = np.lexsort((se[:, 1], se[:, 0]))
+        return dict(step=se[order, 0], env=se[order, 1], r=episodes["r"][:n].cpu().numpy()[order],
+                    l=episodes["l"][:n].cpu().numpy()[order], truncated=episodes["truncated"][:n].cpu().numpy()[order].astype(bool))
 
     @staticmethod
     def terminal_records(terminal):
@@ -398,8 +498,16 @@ class SpaceGymVectorEnv:
         return blob
 
     def load_state(self, blob):
+        """a save_state() blob taken with episode statistics on switches them on and resumes them"""
         blob = np.ascontiguousarray(blob, np.uint8)
         self._ck(self._lib.sg_load_state(self._h, self._ptr(blob), blob.size), "sg_load_state")
+        if self._snapshot_version(blob) == 2 and not self._episode_stats:
+            self._episode_stats = True
+            self._blocks = {}
+
+    @staticmethod
+    def _snapshot_version(blob):
+        return int(np.frombuffer(blob, dtype=np.uint32, count=2)[1])
 
     SNAPSHOT_HEADER_BYTES = 48
 
@@ -407,13 +515,16 @@ class SpaceGymVectorEnv:
         """introspection of a save_state() blob: the engine's per-env columns as NumPy views --
         q0 (x, y, theta, vx), q1 (vy, omega, goal_x, goal_y | orbit angle, eccentricity), ctr (elapsed, episode),
         aux (goal draws, ship_tile | goal_tile << 8 | case_b << 16 | flip << 17, free-tile multiset lo, hi),
-        Goal: pl0 / pl1 (two planets each), cshift (tiling column shifts); KeplerRandomOrbits: orbd (cos, sin of the angle)"""
+        Goal: pl0 / pl1 (two planets each), cshift (tiling column shifts); KeplerRandomOrbits: orbd (cos, sin of the angle);
+        a blob taken with episode statistics on: ep_ret (float64), ep_len (int32), the running return and length"""
         B, off, out = self.num_envs, self.SNAPSHOT_HEADER_BYTES, {}
         cols = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4)]
         if self.spec["family"] == "goal":
             cols += [("pl0", np.float32, 4)] + ([("pl1", np.float32, 4)] if self.n_planets > 2 else []) + [("cshift", np.float32, 4)]
         elif self.env_id == "KeplerRandomOrbits-v0":
             cols += [("orbd", np.float64, 2)]
+        if self._snapshot_version(blob) == 2:
+            cols += [("ep_ret", np.float64, 1), ("ep_len", np.int32, 1)]
         for name, dt, w in cols:
             nb = B * w * np.dtype(dt).itemsize
             out[name] = np.frombuffer(blob, dtype=dt, count=B * w, offset=off).reshape(B, w)
@@ -454,7 +565,7 @@ class SpaceGymVectorEnv:
 
 
 _ENGINE_KWARGS = ("device", "seed", "env_index_base", "max_episode_steps", "auto_reset", "validate_actions", "terminal_observation",
-                  "copy", "steering", "env_kwargs", "from_class")
+                  "copy", "steering", "env_kwargs", "from_class", "episode_statistics")
 
 
 def make_vec(env_id, num_envs=1, **kwargs):

@@ -14,7 +14,8 @@
  *   - no allocation, no host synchronisation and no host<->device copy inside the *_device calls:
  *     they only enqueue kernels on the given stream (hipGraph-capturable);
  *   - the host-buffer calls (sg_reset, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
- *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
+ *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes, sg_set_normalize, sg_get_normalize_state,
+ *     sg_set_normalize_state) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
  *     the caller's streams before, and return when they are complete -- no manual synchronisation between the two kinds;
  *   - a handle is not thread-safe; independent handles are.
  *   - observations/rewards are float32 (the reference returns float64; parity tolerance in DESIGN.md).
@@ -245,6 +246,60 @@ int sg_rollout_device_episodes(sg_env *env, int32_t n_steps, const void *actions
                                uint8_t *done_dev, uint8_t *truncated_dev, const sg_terminal_list *terminal,
                                const sg_episode_list *episodes, void *hip_stream);
 
+/* Running normalization of observations and rewards -- gym 0.21's NormalizeObservation and NormalizeReward (gym/wrappers/
+ * normalize.py; SB3 VecNormalize, CleanRL's PPO) around the vector env, on the device.  With RunningMeanStd(mean 0, var 1,
+ * count 1e-4) and update(x [B, ...]) = { bm, bv = mean and variance (ddof 0) of x over axis 0, n = B; delta = bm - mean;
+ * tot = count + n; mean += delta * n / tot; var = (var * count + bv * n + delta^2 * count * n / tot) / tot; count = tot }:
+ *   observations (obs):  obs_rms.update(obs); obs = (obs - obs_rms.mean) / sqrt(obs_rms.var + epsilon) -- on every step
+ *                        and every reset (the reset batch updates the observation statistics, nothing else);
+ *   rewards (reward):    returns = returns * gamma + reward (float64 [B], one per env); return_rms.update(returns);
+ *                        reward = reward / sqrt(return_rms.var + epsilon); returns[done] = 0 -- on every step, not on reset.
+ * Decisions:
+ *   - statistics and normalized values are float64; each output element is rounded to float32 once; the batch moments of
+ *     the observations are taken over the float32 values promoted to float64 (more exact than NumPy's float32 np.mean);
+ *   - `returns` is a separate multiply and add in float64 per step, in step order: bit-identical to that NumPy loop;
+ *   - a K-step rollout updates K times, once per step row, in step order: exactly what K single steps give.  The reductions
+ *     depend only on (num_envs, obs_dim), so every entry point and rollout kernel gives the same bits;
+ *   - terminal observations (the dense terminal_obs rows of envs with done, sg_terminal_list records, the sg_step_begin block)
+ *     are normalized with the statistics of their own step, after its update, and do not enter it (SB3 VecNormalize);
+ *   - episode statistics and event counters see the raw rewards (RecordEpisodeStatistics inside the normalizers);
+ *   - optional clipping after normalization to [-clip_obs, clip_obs] / [-clip_reward, clip_reward] (+inf: none, the default;
+ *     SB3's clip_obs); update = 0 freezes statistics and returns (evaluation, SB3 training=False): outputs use the statistics
+ *     as they are;
+ *   - sg_reset / sg_seed keep the statistics and returns (as gym).  Switching normalization on from off starts them afresh;
+ *     switching it off frees them; changing gamma / epsilon / clip / update or one of the two flags while on keeps them.
+ * Every call that returns observations or rewards is normalized in place: sg_reset[_device], sg_step[_device], sg_step_begin /
+ * sg_step_end (on the device block, before it is copied: the kernel no longer stores into page-locked memory itself),
+ * sg_rollout_device[_terminal|_episodes] with every rollout plan.  Three kernels follow the call on its stream (per-workgroup
+ * moments of every step row, the running update, the normalization in place); with normalization off nothing is launched or
+ * allocated.  Scratch: about 16 (obs_dim + 1) B per 256 envs and step, allocated for one step when switched on and grown by the
+ * first longer call outside stream capture (or sg_normalize_reserve): a call captured into a graph fails if it would need more.
+ * A captured graph keeps the configuration it was captured with, and switching normalization off invalidates it. */
+typedef struct sg_normalize {
+    uint32_t struct_size;  /* sizeof(sg_normalize), set by sg_normalize_init */
+    int32_t obs;           /* 1: NormalizeObservation */
+    int32_t reward;        /* 1: NormalizeReward */
+    int32_t update;        /* 1: the statistics advance (training); 0: frozen (evaluation) */
+    double gamma;          /* NormalizeReward's discount, in [0, 1] (0.99) */
+    double epsilon;        /* added to the variance under the square root (1e-8) */
+    double clip_obs;       /* > 0; +inf: no clipping (default) */
+    double clip_reward;    /* > 0; +inf: no clipping (default) */
+} sg_normalize;
+/* gym's defaults: obs = reward = update = 1, gamma 0.99, epsilon 1e-8, no clipping. */
+void sg_normalize_init(sg_normalize *cfg);
+/* cfg NULL, or obs and reward both 0: off.  Refused while a step is in flight. */
+int sg_set_normalize(sg_env *env, const sg_normalize *cfg);
+int sg_get_normalize(sg_env *env, sg_normalize *out);  /* obs = reward = 0 while off */
+/* Grows the scratch for calls of up to n_steps steps now, so that such a call can be captured into a graph. */
+int sg_normalize_reserve(sg_env *env, int32_t n_steps);
+/* The running statistics, float64 host arrays (any pointer may be NULL to skip it): obs_mean / obs_var [obs_dim], obs_count,
+ * ret_mean, ret_var, ret_count [1], returns [num_envs].  The getter waits for the enqueued work; the setter (NULL: keep) puts a
+ * policy's statistics into an evaluation env.  Both fail with SG_ERR_INVALID while normalization is off. */
+int sg_get_normalize_state(sg_env *env, double *obs_mean, double *obs_var, double *obs_count, double *ret_mean, double *ret_var,
+                           double *ret_count, double *returns);
+int sg_set_normalize_state(sg_env *env, const double *obs_mean, const double *obs_var, const double *obs_count,
+                           const double *ret_mean, const double *ret_var, const double *ret_count, const double *returns);
+
 /* On-device action source for sg_rollout_device: the uniformly random policy (what the reference's README loop and the
  * benchmark use: env.action_space.sample(), gym spaces Box / Discrete).  Fills actions_dev [n_steps, num_envs, 2] float32
  * with i.i.d. U(-1, 1) values (discrete ids: int32 [n_steps, num_envs] uniform in 0..5).  Entry (t, i) is a function of
@@ -267,7 +322,12 @@ int sg_set_state(sg_env *env, const float *ship, const float *planets, const flo
  * Loading it into a handle of the same env id and batch size makes the following steps bit-identical to those that
  * followed the save.  While episode statistics are on the blob also carries the running return and length of every env
  * (sg_state_bytes grows by 12 B per env; with them off it is what it was before they existed); loading such a blob switches
- * the statistics on and resumes them bit-identically, loading one without them into a handle that has them on zeroes them. */
+ * the statistics on and resumes them bit-identically, loading one without them into a handle that has them on zeroes them.
+ * While normalization is on the blob is header version 3: the version-1 columns, a flags word naming the blocks that follow
+ * (episode statistics, normalization), then those blocks: the configuration, the running statistics and `returns`.  Loading it
+ * switches normalization on with that configuration and resumes it bit-identically; loading a version-1 / 2 blob into a
+ * handle with normalization on starts its statistics afresh and keeps the configuration.  With normalization off the blob is
+ * byte for byte what it was before normalization existed. */
 size_t sg_state_bytes(const sg_env *env);
 int sg_save_state(sg_env *env, void *blob_host, size_t bytes);
 int sg_load_state(sg_env *env, const void *blob_host, size_t bytes);

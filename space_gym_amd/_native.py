@@ -34,6 +34,13 @@ class SgEpisodeList(C.Structure):
                 ("truncated", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class SgNormalize(C.Structure):
+    """sg_normalize (include/spacegym.h): running observation / reward normalization (gym NormalizeObservation /
+    NormalizeReward); sg_normalize_init fills in gym's defaults"""
+    _fields_ = [("struct_size", C.c_uint32), ("obs", C.c_int32), ("reward", C.c_int32), ("update", C.c_int32),
+                ("gamma", C.c_double), ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -74,6 +81,12 @@ SYMBOLS = {
     "sg_step_end_episodes": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "sg_rollout_device_episodes": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList),
                                              C.POINTER(SgEpisodeList), _vp]),
+    "sg_normalize_init": (None, [C.POINTER(SgNormalize)]),
+    "sg_set_normalize": (C.c_int, [_vp, C.POINTER(SgNormalize)]),
+    "sg_get_normalize": (C.c_int, [_vp, C.POINTER(SgNormalize)]),
+    "sg_normalize_reserve": (C.c_int, [_vp, C.c_int32]),
+    "sg_get_normalize_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_set_normalize_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_check_status": (C.c_int, [_vp]),
     "sg_set_counters": (C.c_int, [_vp, C.c_int32]),
     "sg_get_counters": (C.c_int, [_vp, C.POINTER(SgCounters), C.c_int32]),

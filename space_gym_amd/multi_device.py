@@ -15,14 +15,15 @@ import numpy as np
 
 from . import _native
 from .sharded import shard_bounds
-from .vector_env import SpaceGymVectorEnv, _ENGINE_KWARGS
+from .vector_env import SpaceGymVectorEnv, _ENGINE_KWARGS, _NORM_KWARGS
 
 
 class MultiDeviceVectorEnv:
     def __init__(self, env_id, num_envs, devices, seed=0, env_index_base=0, copy=True, **kwargs):
         """devices: GPU indices, one block of envs each (the first is the root: where actions are taken from and results
         land); an index may repeat (several blocks on one GPU: how the tests run it on a one-GPU box).  kwargs: make_vec's,
-        except episode_statistics: the per-device blocks do not gather episode statistics yet."""
+        except episode_statistics and the normalization keywords: the per-device blocks do not gather episode statistics yet,
+        and running statistics over all blocks need a cross-device reduction."""
         import torch
         self._torch = torch
         self.devices = [int(d) for d in devices]
@@ -37,6 +38,10 @@ class MultiDeviceVectorEnv:
         engine.pop("device", None)
         if engine.pop("episode_statistics", False):
             raise NotImplementedError("episode_statistics: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device has them)")
+        norm = {k: engine.pop(k) for k in _NORM_KWARGS if k in engine}
+        if norm.get("normalize_obs") or norm.get("normalize_reward"):
+            raise NotImplementedError("normalize_obs / normalize_reward: not served by MultiDeviceVectorEnv (statistics over all "
+                                      "devices need a cross-device reduction; one SpaceGymVectorEnv per device has them)")
         engine.setdefault("terminal_observation", False)
         # a template block gives the native config and parameter block (and validates the keywords); sg_create_sharded_ex
         # then makes the real handles: contiguous blocks, env_index_base of block k = env_index_base + its first env

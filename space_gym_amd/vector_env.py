@@ -17,6 +17,10 @@ Two I/O modes:
 Episode statistics (`episode_statistics=True` / `set_episode_statistics`): the return and length of every finished episode,
 with gym.wrappers.RecordEpisodeStatistics' semantics, summed on the device by a pass behind every stepping call --
 `info["episode"]` / `info["_episode"]` of step(), `episodes=` of step_torch and rollout_torch.
+
+Normalization (`normalize_obs=True` / `normalize_reward=True`, `set_normalization`): gym's NormalizeObservation and
+NormalizeReward with running float64 statistics on the device; every call that returns observations or rewards returns them
+normalized (reset, step, step_torch, rollout_torch, prepare_rollout), terminal observations included.
 """
 import ctypes as C
 
@@ -26,6 +30,9 @@ from . import _native
 from .registration import (ENV_CLASSES, ENV_SPECS, constructor_kwargs, is_discrete, obs_dim, single_action_space,
                            single_observation_space)
 from .spaces import MultiDiscrete, batch_box
+
+
+_KEEP = object()  # set_normalization: leave the value as it is
 
 
 class StepInfo(dict):
@@ -40,7 +47,8 @@ class SpaceGymVectorEnv:
 
     def __init__(self, env_id, num_envs, device=0, seed=0, env_index_base=0, max_episode_steps=None, auto_reset=True,
                  validate_actions=True, terminal_observation=True, copy=True, steering=None, env_kwargs=None, from_class=False,
-                 episode_statistics=False, _handle=None):
+                 episode_statistics=False, normalize_obs=False, normalize_reward=False, norm_gamma=0.99, norm_epsilon=1e-8,
+                 clip_obs=None, clip_reward=None, _handle=None):
         """steering: "velocity" (ship_steering=1, what every registered id uses) or "acceleration" (ship_steering=0, the
         constructor default of the reference classes: omega is a state, the thruster a torque); None: what env_kwargs say.
         env_kwargs: keyword arguments of the reference's constructor (GoalEnv.__init__ goal.py:18-31, KeplerEnv.__init__
@@ -52,7 +60,9 @@ class SpaceGymVectorEnv:
         device-tensor calls never validate: that would need a device-to-host synchronisation).
         copy=False: reset()/step() return views of the engine's pinned output buffers, overwritten by the next call
         (no per-step allocation or copy); copy=True returns fresh arrays like gym's vector envs.
-        episode_statistics: switch the episode statistics on from the start (set_episode_statistics)."""
+        episode_statistics: switch the episode statistics on from the start (set_episode_statistics).
+        normalize_obs / normalize_reward, norm_gamma, norm_epsilon, clip_obs, clip_reward: switch normalization on from the start
+        (set_normalization)."""
         if env_id not in ENV_SPECS:
             raise ValueError(f"unknown env id {env_id!r}; served ids: {sorted(ENV_SPECS)}")
         self._lib = _native.load()
@@ -101,6 +111,9 @@ class SpaceGymVectorEnv:
         self._episode_stats = False
         if episode_statistics:
             self.set_episode_statistics(True)
+        if normalize_obs or normalize_reward:
+            self.set_normalization(obs=normalize_obs, reward=normalize_reward, gamma=norm_gamma, epsilon=norm_epsilon,
+                                   clip_obs=clip_obs, clip_reward=clip_reward)
 
     def _native_params(self, kw):
         """sg_params (include/spacegym.h) from the constructor's keyword arguments"""
@@ -184,6 +197,70 @@ class SpaceGymVectorEnv:
     def _need_episode_stats(self, what):
         if not self._episode_stats:
             raise ValueError(f"{what}: episode statistics are off (make_vec(..., episode_statistics=True) or set_episode_statistics())")
+
+    def normalization(self):
+        """the normalization configuration (sg_get_normalize) as a dict: obs, reward, update (bool), gamma, epsilon, clip_obs,
+        clip_reward (None: no clipping)"""
+        n = _native.SgNormalize()
+        self._ck(self._lib.sg_get_normalize(self._h, C.byref(n)), "sg_get_normalize")
+        clip = lambda v: None if v == float("inf") else v  # noqa: E731
+        return dict(obs=bool(n.obs), reward=bool(n.reward), update=bool(n.update), gamma=n.gamma, epsilon=n.epsilon,
+                    clip_obs=clip(n.clip_obs), clip_reward=clip(n.clip_reward))
+
+    def set_normalization(self, obs=None, reward=None, update=None, gamma=None, epsilon=None, clip_obs=_KEEP, clip_reward=_KEEP):
+        """gym.wrappers.NormalizeObservation (obs) and NormalizeReward (reward) on the device (sg_set_normalize): running float64
+        mean and variance of the observations and of the discounted return, updated by every step and (observations) reset.
+        Arguments left out keep their value; clip_obs / clip_reward None: no clipping.  update=False freezes the statistics
+        (evaluation).  Switching on from off starts the statistics afresh, switching both off frees them."""
+        if self._pending:
+            raise RuntimeError("set_normalization() while a step is in flight (step_wait() first)")
+        cur = self.normalization()
+        new = dict(obs=cur["obs"] if obs is None else bool(obs), reward=cur["reward"] if reward is None else bool(reward),
+                   update=cur["update"] if update is None else bool(update), gamma=cur["gamma"] if gamma is None else float(gamma),
+                   epsilon=cur["epsilon"] if epsilon is None else float(epsilon),
+                   clip_obs=cur["clip_obs"] if clip_obs is _KEEP else clip_obs,
+                   clip_reward=cur["clip_reward"] if clip_reward is _KEEP else clip_reward)
+        if not 0.0 <= new["gamma"] <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {new['gamma']}")
+        if not 0.0 <= new["epsilon"] < float("inf"):
+            raise ValueError(f"epsilon must be finite and >= 0, got {new['epsilon']}")
+        for k in ("clip_obs", "clip_reward"):
+            if new[k] is not None and not float(new[k]) > 0.0:
+                raise ValueError(f"{k} must be > 0 or None, got {new[k]}")
+        n = _native.SgNormalize()
+        self._lib.sg_normalize_init(C.byref(n))
+        n.obs, n.reward, n.update = int(new["obs"]), int(new["reward"]), int(new["update"])
+        n.gamma, n.epsilon = new["gamma"], new["epsilon"]
+        n.clip_obs = float("inf") if new["clip_obs"] is None else float(new["clip_obs"])
+        n.clip_reward = float("inf") if new["clip_reward"] is None else float(new["clip_reward"])
+        self._ck(self._lib.sg_set_normalize(self._h, C.byref(n)), "sg_set_normalize")
+
+    _NORM_KEYS = ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count", "returns")
+
+    def _norm_shapes(self):
+        return dict(obs_mean=(self.obs_dim,), obs_var=(self.obs_dim,), obs_count=(), ret_mean=(), ret_var=(), ret_count=(),
+                    returns=(self.num_envs,))
+
+    def normalizer_state(self):
+        """the running statistics (sg_get_normalize_state) as float64 NumPy arrays: obs_mean, obs_var [D], obs_count, ret_mean,
+        ret_var, ret_count (0-d) and returns [B]; waits for the enqueued work"""
+        out = {k: np.zeros(s, np.float64) for k, s in self._norm_shapes().items()}
+        self._ck(self._lib.sg_get_normalize_state(self._h, *[self._ptr(out[k]) for k in self._NORM_KEYS]), "sg_get_normalize_state")
+        return out
+
+    def set_normalizer_state(self, state):
+        """puts statistics (a normalizer_state() dict; missing keys keep their value) into this env, e.g. a trained policy's
+        into an evaluation env"""
+        args = []
+        for k, shape in self._norm_shapes().items():
+            if k in state and state[k] is not None:
+                a = np.array(state[k], np.float64, order="C")  # (ascontiguousarray would make a 0-d value 1-d)
+                if a.shape != shape:
+                    raise ValueError(f"{k}: expected shape {shape}, got {a.shape}")
+                args.append(a)
+            else:
+                args.append(None)
+        self._ck(self._lib.sg_set_normalize_state(self._h, *[self._ptr(a) for a in args]), "sg_set_normalize_state")
 
     def set_auto_reset(self, on):
         self._ck(self._lib.sg_set_auto_reset(self._h, int(bool(on))), "sg_set_auto_reset")
@@ -430,6 +507,8 @@ class SpaceGymVectorEnv:
         self._check_tensor("done", done, torch.uint8, (K, B))
         self._check_tensor("trunc", trunc, torch.uint8, (K, B))
         el = self._episode_list_arg(episodes) if episodes is not None else None
+        # (normalization on: its scratch for K steps is made now, so that the callable can be captured into a graph)
+        self._ck(self._lib.sg_normalize_reserve(self._h, K), "sg_normalize_reserve")
         keep = (actions, obs, reward, done, trunc)  # the callable keeps the tensors alive
         args = (self._h, K) + tuple(C.c_void_p(t.data_ptr()) for t in keep)
         fn, what, ck, dev = self._lib.sg_rollout_device, "sg_rollout_device", self._ck, self.device
@@ -501,9 +580,28 @@ class SpaceGymVectorEnv:
         """a save_state() blob taken with episode statistics on switches them on and resumes them"""
         blob = np.ascontiguousarray(blob, np.uint8)
         self._ck(self._lib.sg_load_state(self._h, self._ptr(blob), blob.size), "sg_load_state")
-        if self._snapshot_version(blob) == 2 and not self._episode_stats:
+        if self._snapshot_has_episodes(blob) and not self._episode_stats:
             self._episode_stats = True
             self._blocks = {}
+
+    def _snapshot_has_episodes(self, blob):
+        v = self._snapshot_version(blob)
+        return v == 2 or (v == 3 and bool(self._snapshot_flags(blob) & 1))
+
+    def _snapshot_flags(self, blob):
+        """the flags word of a version-3 blob (1: episode block, 2: normalization block), right after the columns"""
+        return int(np.frombuffer(blob, dtype=np.uint32, count=1, offset=self.SNAPSHOT_HEADER_BYTES + self._column_bytes())[0])
+
+    def _snapshot_column_specs(self):
+        cols = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4)]
+        if self.spec["family"] == "goal":
+            cols += [("pl0", np.float32, 4)] + ([("pl1", np.float32, 4)] if self.n_planets > 2 else []) + [("cshift", np.float32, 4)]
+        elif self.env_id == "KeplerRandomOrbits-v0":
+            cols += [("orbd", np.float64, 2)]
+        return cols
+
+    def _column_bytes(self):
+        return sum(self.num_envs * w * np.dtype(dt).itemsize for _, dt, w in self._snapshot_column_specs())
 
     @staticmethod
     def _snapshot_version(blob):
@@ -516,19 +614,31 @@ class SpaceGymVectorEnv:
         q0 (x, y, theta, vx), q1 (vy, omega, goal_x, goal_y | orbit angle, eccentricity), ctr (elapsed, episode),
         aux (goal draws, ship_tile | goal_tile << 8 | case_b << 16 | flip << 17, free-tile multiset lo, hi),
         Goal: pl0 / pl1 (two planets each), cshift (tiling column shifts); KeplerRandomOrbits: orbd (cos, sin of the angle);
-        a blob taken with episode statistics on: ep_ret (float64), ep_len (int32), the running return and length"""
+        a blob taken with episode statistics on: ep_ret (float64), ep_len (int32), the running return and length;
+        one taken with normalization on (version 3): flags, norm_config (sg_normalize bytes), norm_mean / norm_var /
+        norm_count (float64 [D + 1], the last entry the return's) and norm_returns (float64 [B])"""
         B, off, out = self.num_envs, self.SNAPSHOT_HEADER_BYTES, {}
-        cols = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4)]
-        if self.spec["family"] == "goal":
-            cols += [("pl0", np.float32, 4)] + ([("pl1", np.float32, 4)] if self.n_planets > 2 else []) + [("cshift", np.float32, 4)]
-        elif self.env_id == "KeplerRandomOrbits-v0":
-            cols += [("orbd", np.float64, 2)]
-        if self._snapshot_version(blob) == 2:
+        cols = self._snapshot_column_specs()
+        version = self._snapshot_version(blob)
+        flags = self._snapshot_flags(blob) if version == 3 else (1 if version == 2 else 0)
+        if version == 3:
+            cols += [("flags", np.uint32, 2)]
+        if flags & 1:
             cols += [("ep_ret", np.float64, 1), ("ep_len", np.int32, 1)]
         for name, dt, w in cols:
-            nb = B * w * np.dtype(dt).itemsize
-            out[name] = np.frombuffer(blob, dtype=dt, count=B * w, offset=off).reshape(B, w)
+            n = (1 if name == "flags" else B) * w
+            out[name] = np.frombuffer(blob, dtype=dt, count=n, offset=off).reshape(-1, w)
+            off += n * np.dtype(dt).itemsize
+        if flags & 2:
+            nb = C.sizeof(_native.SgNormalize)
+            out["norm_config"] = blob[off:off + nb]
             off += nb
+            S = self.obs_dim + 1
+            for name in ("norm_mean", "norm_var", "norm_count"):
+                out[name] = np.frombuffer(blob, dtype=np.float64, count=S, offset=off)
+                off += 8 * S
+            out["norm_returns"] = np.frombuffer(blob, dtype=np.float64, count=B, offset=off)
+            off += 8 * B
         assert off == blob.size, (off, blob.size)
         return out
 
@@ -565,7 +675,10 @@ class SpaceGymVectorEnv:
 
 
 _ENGINE_KWARGS = ("device", "seed", "env_index_base", "max_episode_steps", "auto_reset", "validate_actions", "terminal_observation",
-                  "copy", "steering", "env_kwargs", "from_class", "episode_statistics")
+                  "copy", "steering", "env_kwargs", "from_class", "episode_statistics", "normalize_obs", "normalize_reward",
+                  "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
+# the normalization keywords, which the multi-device front ends do not serve yet (a cross-device reduction is needed)
+_NORM_KWARGS = ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
 
 
 def make_vec(env_id, num_envs=1, **kwargs):

@@ -15,7 +15,7 @@
  *     they only enqueue kernels on the given stream (hipGraph-capturable);
  *   - the host-buffer calls (sg_reset, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
  *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes, sg_set_normalize, sg_get_normalize_state,
- *     sg_set_normalize_state) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
+ *     sg_set_normalize_state, sg_render) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
  *     the caller's streams before, and return when they are complete -- no manual synchronisation between the two kinds;
  *   - a handle is not thread-safe; independent handles are.
  *   - observations/rewards are float32 (the reference returns float64; parity tolerance in DESIGN.md).
@@ -299,6 +299,42 @@ int sg_get_normalize_state(sg_env *env, double *obs_mean, double *obs_var, doubl
                            double *ret_count, double *returns);
 int sg_set_normalize_state(sg_env *env, const double *obs_mean, const double *obs_var, const double *obs_count,
                            const double *ret_mean, const double *ret_var, const double *ret_count, const double *returns);
+
+/* render(mode="rgb_array") -- SpaceshipEnv.render (spaceship_env.py:80-90) with gym_space/rendering.py:15-182 -- for chosen envs
+ * of the batch, drawn on the device: uint8 frames [n, size, size, 3] (HWC, row 0 the top, as gym's rgb_array).  The scene is the
+ * reference's: planet outlines (rendering.py:79-86; Kepler: the planet and the border circle, kepler.py:204-206,215), the ship's
+ * engine, exhaust with alpha = thrust, body, outline and centre (:88-132), the goal's x (:140-146), a procedural stand-in for
+ * the torque image (assets/torque_img.png is not shipped, :53-54,134-138), the trace of the last positions (:21-22,158-165) and,
+ * for the Goal ids (debug_mode, goal.py:71), the lidar lines (:72-76,170-182).  Lengths the reference gives in pixels are scaled
+ * by size / 600 (MAX_SCREEN_SIZE, :11).  DESIGN section 11 states the scene, the rasterisation rules (fixed-point, integer
+ * coverage) and the trace semantics; tests/render_model.py implements them in NumPy, bit for bit.
+ *
+ * The trace (Renderer.prev_ship_pos) lives in `capacity` slots: slot k of a call belongs to env_ids[k]; each call appends the
+ * env's current position to it.  A slot starts empty again when its env id differs from its previous call's, when the env's
+ * episode changed since (Renderer.reset on env.reset(), auto-reset inside the stepping calls included), or after sg_reset,
+ * sg_reset_device, sg_set_state or sg_load_state.  The trace is presentation state: snapshots do not carry it.
+ * With rendering off (the default) nothing is allocated or launched for it. */
+typedef struct sg_render_config {
+    uint32_t struct_size;  /* sizeof(sg_render_config), set by sg_render_config_init */
+    int32_t capacity;      /* trace slots = most frames per call (1 .. 1048576) */
+    int32_t trace_len;     /* num_prev_pos_vis (rendering.py:21); -1: the family's (Goal 30, Kepler 75, kepler.py:222); 0: no trace; <= 256 */
+    int32_t debug_lidar;   /* -1: the family's (Goal 1, goal.py:71; Kepler 0); 1 is refused for Kepler, which has no lidar */
+    double trace_decay;    /* prev_pos_color_decay (rendering.py:22) in [0, 1]; NaN: the family's (0.85 / 0.95, kepler.py:222) */
+} sg_render_config;
+/* capacity 1, every other field "the family's". */
+void sg_render_config_init(sg_render_config *cfg);
+/* cfg NULL: off, frees the slots.  Switching on (again) starts every slot empty.  Waits for the handle's enqueued work. */
+int sg_set_render(sg_env *env, const sg_render_config *cfg);
+/* n frames (n <= capacity) of the envs env_ids [n] (int32), size x size pixels (16 .. 2048), into frames [n, size, size, 3] uint8.
+ * actions: the step's own layout for the whole batch ([num_envs, 2] float32, or [num_envs] int32 for the discrete ids), read for
+ * the exhaust and the torque indicator of the frames' envs -- the last action, as the reference's last_action
+ * (spaceship_env.py:73); NULL: none (thrust = torque = 0, as before the first step).
+ * sg_render_device enqueues two kernels on the stream and allocates nothing (hipGraph-capturable); an env id outside the batch
+ * gives a white frame and sets the handle's status word, which sg_check_status reports (SG_ERR_INVALID) and clears.  sg_render
+ * (host arrays) refuses such ids up front. */
+int sg_render_device(sg_env *env, int32_t n, const int32_t *env_ids_dev, const void *actions_dev, int32_t size,
+                     uint8_t *frames_dev, void *hip_stream);
+int sg_render(sg_env *env, int32_t n, const int32_t *env_ids_host, const void *actions_host, int32_t size, uint8_t *frames_host);
 
 /* On-device action source for sg_rollout_device: the uniformly random policy (what the reference's README loop and the
  * benchmark use: env.action_space.sample(), gym spaces Box / Discrete).  Fills actions_dev [n_steps, num_envs, 2] float32

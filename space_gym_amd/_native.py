@@ -41,6 +41,13 @@ class SgNormalize(C.Structure):
                 ("gamma", C.c_double), ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double)]
 
 
+class SgRenderConfig(C.Structure):
+    """sg_render_config (include/spacegym.h): render(mode="rgb_array") on the device; sg_render_config_init fills in capacity 1
+    and the family's trace length, decay and lidar switch (-1 / NaN)"""
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_int32), ("trace_len", C.c_int32), ("debug_lidar", C.c_int32),
+                ("trace_decay", C.c_double)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -87,6 +94,10 @@ SYMBOLS = {
     "sg_normalize_reserve": (C.c_int, [_vp, C.c_int32]),
     "sg_get_normalize_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_set_normalize_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_render_config_init": (None, [C.POINTER(SgRenderConfig)]),
+    "sg_set_render": (C.c_int, [_vp, C.POINTER(SgRenderConfig)]),
+    "sg_render_device": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "sg_render": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),
     "sg_check_status": (C.c_int, [_vp]),
     "sg_set_counters": (C.c_int, [_vp, C.c_int32]),
     "sg_get_counters": (C.c_int, [_vp, C.POINTER(SgCounters), C.c_int32]),

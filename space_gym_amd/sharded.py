@@ -35,9 +35,11 @@ class ShardedVectorEnv:
 
     def __init__(self, env_id, num_envs, seed=0, group=None, device=None, local_env=None, terminal_observation=False, copy=True,
                  **kwargs):
-        """kwargs: make_vec's (engine keywords and the reference's constructor kwargs) except episode_statistics and
-        normalization, which the gather does not carry yet (a rank's own SpaceGymVectorEnv has them).  copy:
+        """kwargs: make_vec's (engine keywords and the reference's constructor kwargs) except episode_statistics, normalization
+        and render, which the gather does not carry yet (a rank's own SpaceGymVectorEnv has them).  copy:
         see the module docstring."""
+        if kwargs.get("render"):
+            raise NotImplementedError("render: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv renders its envs)")
         if kwargs.get("episode_statistics"):
             raise NotImplementedError("episode_statistics: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv has them)")
         norm = {k: kwargs.pop(k) for k in ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs",

@@ -21,6 +21,9 @@ with gym.wrappers.RecordEpisodeStatistics' semantics, summed on the device by a 
 Normalization (`normalize_obs=True` / `normalize_reward=True`, `set_normalization`): gym's NormalizeObservation and
 NormalizeReward with running float64 statistics on the device; every call that returns observations or rewards returns them
 normalized (reset, step, step_torch, rollout_torch, prepare_rollout), terminal observations included.
+
+Rendering (`render=True` / `render=dict(...)`, `set_render`): `render(mode="rgb_array")` of the reference's Renderer
+(gym_space/rendering.py) for chosen envs, drawn on the device -- `render()` (NumPy) and `render_torch()` (device tensor).
 """
 import ctypes as C
 
@@ -42,13 +45,43 @@ class StepInfo(dict):
     A per-env list of dicts (old gym VectorEnv) would cost more than the step itself at B = 65536."""
 
 
+# rendering: the largest frame side, and the Python default for the number of trace slots (frames per call)
+RENDER_SIZES = (16, 2048)
+RENDER_CAPACITY = 16
+
+
+def render_config(family, capacity=RENDER_CAPACITY, trace_len=None, trace_decay=None, debug_lidar=None):
+    """Checks set_render's keywords and returns them as the native config takes them (-1 / NaN: the family's value).
+    family: "goal" or "kepler"."""
+    capacity = int(capacity)
+    if not 1 <= capacity <= 1 << 20:
+        raise ValueError(f"capacity must be in 1 .. {1 << 20}, got {capacity}")
+    trace_len = -1 if trace_len is None else int(trace_len)
+    if not -1 <= trace_len <= 256:
+        raise ValueError(f"trace_len must be in 0 .. 256 (None: the family's), got {trace_len}")
+    trace_decay = float("nan") if trace_decay is None else float(trace_decay)
+    if not (np.isnan(trace_decay) or 0.0 <= trace_decay <= 1.0):
+        raise ValueError(f"trace_decay must be in [0, 1] (None: the family's), got {trace_decay}")
+    debug_lidar = -1 if debug_lidar is None else int(bool(debug_lidar))
+    if debug_lidar == 1 and family != "goal":
+        raise ValueError("debug_lidar: the Kepler ids have no lidar")
+    return dict(capacity=capacity, trace_len=trace_len, trace_decay=trace_decay, debug_lidar=debug_lidar)
+
+
+def check_render_size(size):
+    size = int(size)
+    if not RENDER_SIZES[0] <= size <= RENDER_SIZES[1]:
+        raise ValueError(f"size must be in {RENDER_SIZES[0]} .. {RENDER_SIZES[1]}, got {size}")
+    return size
+
+
 class SpaceGymVectorEnv:
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, env_id, num_envs, device=0, seed=0, env_index_base=0, max_episode_steps=None, auto_reset=True,
                  validate_actions=True, terminal_observation=True, copy=True, steering=None, env_kwargs=None, from_class=False,
                  episode_statistics=False, normalize_obs=False, normalize_reward=False, norm_gamma=0.99, norm_epsilon=1e-8,
-                 clip_obs=None, clip_reward=None, _handle=None):
+                 clip_obs=None, clip_reward=None, render=False, _handle=None):
         """steering: "velocity" (ship_steering=1, what every registered id uses) or "acceleration" (ship_steering=0, the
         constructor default of the reference classes: omega is a state, the thruster a torque); None: what env_kwargs say.
         env_kwargs: keyword arguments of the reference's constructor (GoalEnv.__init__ goal.py:18-31, KeplerEnv.__init__
@@ -62,7 +95,8 @@ class SpaceGymVectorEnv:
         (no per-step allocation or copy); copy=True returns fresh arrays like gym's vector envs.
         episode_statistics: switch the episode statistics on from the start (set_episode_statistics).
         normalize_obs / normalize_reward, norm_gamma, norm_epsilon, clip_obs, clip_reward: switch normalization on from the start
-        (set_normalization)."""
+        (set_normalization).
+        render: True or a dict of set_render's keywords (capacity, trace_len, trace_decay, debug_lidar): switch rendering on."""
         if env_id not in ENV_SPECS:
             raise ValueError(f"unknown env id {env_id!r}; served ids: {sorted(ENV_SPECS)}")
         self._lib = _native.load()
@@ -109,6 +143,10 @@ class SpaceGymVectorEnv:
         self._blocks = {}
         self._torch_bufs = None
         self._episode_stats = False
+        self._render_on = False
+        self._have_act = False  # a step() has filled the pinned action buffer: render() shows that action
+        if render:
+            self.set_render(True, **(render if isinstance(render, dict) else {}))
         if episode_statistics:
             self.set_episode_statistics(True)
         if normalize_obs or normalize_reward:
@@ -262,6 +300,79 @@ class SpaceGymVectorEnv:
                 args.append(None)
         self._ck(self._lib.sg_set_normalize_state(self._h, *[self._ptr(a) for a in args]), "sg_set_normalize_state")
 
+    # ------------------------------------------------------------------ rendering
+    def set_render(self, on=True, capacity=RENDER_CAPACITY, trace_len=None, trace_decay=None, debug_lidar=None):
+        """render(mode="rgb_array") on the device (sg_set_render).  capacity: trace slots, the most frames per call; trace_len
+        (num_prev_pos_vis), trace_decay (prev_pos_color_decay), debug_lidar: None keeps the family's (Goal 30, 0.85, lidar
+        lines; Kepler 75, 0.95, none: rendering.py:21-22, goal.py:71, kepler.py:222).  Switching on (again) empties every trace
+        slot; off frees them."""
+        if self._pending:
+            raise RuntimeError("set_render() while a step is in flight (step_wait() first)")
+        if not on:
+            self._ck(self._lib.sg_set_render(self._h, None), "sg_set_render")
+            self._render_on = False
+            return
+        v = render_config(self.spec["family"], capacity, trace_len, trace_decay, debug_lidar)
+        cfg = _native.SgRenderConfig()
+        self._lib.sg_render_config_init(C.byref(cfg))
+        for k, x in v.items():
+            setattr(cfg, k, x)
+        self._ck(self._lib.sg_set_render(self._h, C.byref(cfg)), "sg_set_render")
+        self._render_on = True
+        self._render_capacity = v["capacity"]
+
+    def _need_render(self, env_ids, what):
+        if not self._render_on:
+            raise ValueError(f"{what}: rendering is off (make_vec(..., render=True) or set_render())")
+        if len(env_ids) > self._render_capacity:
+            raise ValueError(f"{what}: {len(env_ids)} frames, capacity {self._render_capacity} (set_render(capacity=...))")
+
+    def render(self, mode="rgb_array", env_ids=(0,), size=600):
+        """SpaceshipEnv.render(mode="rgb_array") (spaceship_env.py:80-90) of the envs `env_ids`: uint8 [n, size, size, 3], row 0
+        the top.  The exhaust and the torque indicator show the actions of the last step() (none before the first).  Every
+        call appends the envs' positions to their traces.  mode="human" (a window) is not served."""
+        if mode == "human":
+            raise NotImplementedError('render(mode="human") opens a window: not served, use mode="rgb_array"')
+        if mode != "rgb_array":
+            raise ValueError(f"unknown render mode {mode!r}; served: {self.metadata['render.modes']}")
+        size = check_render_size(size)
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(env_ids)), dtype=np.int32)
+        if ids.ndim != 1:
+            raise ValueError("env_ids must be a sequence of env indices")
+        if np.any(ids < 0) or np.any(ids >= self.num_envs):
+            raise ValueError(f"env_ids must be in 0 .. {self.num_envs - 1}")
+        if self._pending:
+            raise RuntimeError("render() while a step is in flight (step_wait() first)")
+        self._need_render(ids, "render")
+        out = np.empty((len(ids), size, size, 3), np.uint8)
+        act = self._act if self._have_act else None
+        self._ck(self._lib.sg_render(self._h, len(ids), self._ptr(ids), self._ptr(act), size, self._ptr(out)), "sg_render")
+        return out
+
+    def render_torch(self, env_ids, actions=None, size=600, out=None):
+        """render() on torch's current stream, without synchronisation (sg_render_device): env_ids an int32 device tensor (or a
+        sequence, copied to the device), actions the step's layout for the whole batch ([B, 2] float32 / [B] int32) or None,
+        out a uint8 device tensor [n, size, size, 3] (allocated if None).  With tensors passed in, the call allocates nothing and
+        can be captured into a graph.  An id outside the batch gives a white frame and an error from check_status()."""
+        import torch
+        size = check_render_size(size)
+        dev = torch.device("cuda", self.device)
+        if not isinstance(env_ids, torch.Tensor):
+            env_ids = torch.as_tensor(np.atleast_1d(np.asarray(env_ids, np.int32)), device=dev)
+        self._check_tensor("env_ids", env_ids, torch.int32, (env_ids.shape[0],) if env_ids.dim() == 1 else (-1,))
+        n = env_ids.shape[0]
+        self._need_render(range(n), "render_torch")
+        if actions is not None:
+            self._check_tensor("actions", actions, torch.int32 if self.discrete else torch.float32,
+                               (self.num_envs,) if self.discrete else (self.num_envs, 2))
+        if out is None:
+            out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=dev)
+        self._check_tensor("out", out, torch.uint8, (n, size, size, 3))
+        self._ck(self._lib.sg_render_device(self._h, n, C.c_void_p(env_ids.data_ptr()),
+                                            C.c_void_p(actions.data_ptr()) if actions is not None else None, size,
+                                            C.c_void_p(out.data_ptr()), self._stream()), "sg_render_device")
+        return out
+
     def set_auto_reset(self, on):
         self._ck(self._lib.sg_set_auto_reset(self._h, int(bool(on))), "sg_set_auto_reset")
 
@@ -296,6 +407,7 @@ class SpaceGymVectorEnv:
         if self._pending:
             raise RuntimeError("step_async() while a step is in flight (step_wait() first)")
         np.copyto(self._act, self._check_actions(actions))  # into the pinned action buffer (unchanged until step_wait)
+        self._have_act = True
         self._ck(self._lib.sg_step_begin(self._h, self._ptr(self._act), int(self.want_terminal_obs)), "sg_step_begin")
         self._pending = True
 
@@ -676,7 +788,7 @@ class SpaceGymVectorEnv:
 
 _ENGINE_KWARGS = ("device", "seed", "env_index_base", "max_episode_steps", "auto_reset", "validate_actions", "terminal_observation",
                   "copy", "steering", "env_kwargs", "from_class", "episode_statistics", "normalize_obs", "normalize_reward",
-                  "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
+                  "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward", "render")
 # the normalization keywords, which the multi-device front ends do not serve yet (a cross-device reduction is needed)
 _NORM_KWARGS = ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
 

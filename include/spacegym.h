@@ -13,7 +13,7 @@
  *     device memory on the handle's GPU, owned by the caller;
  *   - no allocation, no host synchronisation and no host<->device copy inside the *_device calls:
  *     they only enqueue kernels on the given stream (hipGraph-capturable);
- *   - the host-buffer calls (sg_reset, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
+ *   - the host-buffer calls (sg_reset, sg_reset_masked, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
  *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes, sg_set_normalize, sg_get_normalize_state,
  *     sg_set_normalize_state, sg_render) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
  *     the caller's streams before, and return when they are complete -- no manual synchronisation between the two kinds;
@@ -117,6 +117,24 @@ int sg_set_auto_reset(sg_env *env, int32_t on);
 /* SpaceshipEnv.reset (spaceship_env.py:59-66) for every env; obs is float32 [num_envs, obs_dim]. */
 int sg_reset(sg_env *env, float *obs_host);
 int sg_reset_device(sg_env *env, float *obs_dev, void *hip_stream);
+
+/* SpaceshipEnv.reset for the envs whose mask byte is nonzero (what auto-reset would start next for each of them);
+ * rows of obs of the other envs are left untouched.  mask uint8 [num_envs], obs float32 [num_envs, obs_dim].
+ * gymnasium's reset(options={"reset_mask": mask}) / envpool's reset(env_id) / reset_idx, for a loop with auto_reset off.
+ * Env i with a nonzero byte starts episode e = (its episode counter) + 1 -- the one auto-reset would start, the one a full
+ * sg_reset starts -- from the reset sampler keyed by (seed, env_index_base + i, e), bit-identical to what auto-reset would write
+ * (the step kernels' own restart code); its elapsed counter goes to 0, its episode queue (rollout kernels) is emptied and
+ * row i of obs receives the episode's first observation.  Envs with byte 0: no column, counter or obs row changes.
+ *   episode statistics (on): the masked envs' running return and length go back to 0; the abandoned episodes give no record;
+ *   normalization (on): the observation statistics are updated with the masked rows only (a batch of popcount(mask) rows; none:
+ *     no update), then those rows are normalized; update = 0 only normalizes; the returns and their statistics stay;
+ *   rendering: a masked env's trace starts afresh (its episode changed), the other envs' traces stay;
+ *   event counters count nothing.
+ * Refused (SG_ERR_INVALID) on a handle not reset since sg_create / sg_seed.  sg_reset_masked_device enqueues a few kernels and
+ * allocates nothing (hipGraph-capturable); sg_reset_masked (host arrays) sends obs up and back, so its other rows come back as
+ * they were. */
+int sg_reset_masked(sg_env *env, const uint8_t *mask_host, float *obs_host);
+int sg_reset_masked_device(sg_env *env, const uint8_t *mask_dev, float *obs_dev, void *hip_stream);
 
 /* SpaceshipEnv.step (spaceship_env.py:68-78) for every env, plus what gym.wrappers.TimeLimit and a
  * VectorEnv add around it (elapsed-step counter, truncation, auto-reset).

@@ -75,6 +75,8 @@ SYMBOLS = {
     "sg_set_auto_reset": (C.c_int, [_vp, C.c_int32]),
     "sg_reset": (C.c_int, [_vp, _vp]),
     "sg_reset_device": (C.c_int, [_vp, _vp, _vp]),
+    "sg_reset_masked": (C.c_int, [_vp, _vp, _vp]),
+    "sg_reset_masked_device": (C.c_int, [_vp, _vp, _vp, _vp]),
     "sg_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_step_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_step_begin": (C.c_int, [_vp, _vp, C.c_int32]),

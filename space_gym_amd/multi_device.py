@@ -108,8 +108,11 @@ class MultiDeviceVectorEnv:
             cur.wait_event(ev)
 
     # ------------------------------------------------------------------ device-tensor path
-    def reset_torch(self):
+    def reset_torch(self, mask=None):
         """first observations of all envs: float32 [num_envs, obs_dim] on the root device"""
+        if mask is not None:
+            raise NotImplementedError("reset(mask=...): not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device resets "
+                                      "chosen envs)")
         self._cur ^= 1
         obs = self._sets[self._cur][0]
 
@@ -174,8 +177,8 @@ class MultiDeviceVectorEnv:
         return self._hand_out(fields)
 
     # ------------------------------------------------------------------ NumPy convenience, lifecycle
-    def reset(self):
-        return self.reset_torch().cpu().numpy()
+    def reset(self, mask=None):
+        return self.reset_torch(mask=mask).cpu().numpy()
 
     def step(self, actions):
         """NumPy in / out like SpaceGymVectorEnv.step: (obs, reward, done, info)"""

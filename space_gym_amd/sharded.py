@@ -117,8 +117,10 @@ class ShardedVectorEnv:
                 q.wait()
         return self._hand_out(fields) if self.rank == 0 else None
 
-    def reset(self):
+    def reset(self, mask=None):
         """Rank 0 gets the first observations of all envs ([num_envs, obs_dim]; copy=False: valid until the call after next), other ranks None."""
+        if mask is not None:
+            raise NotImplementedError("reset(mask=...): not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv resets chosen envs)")
         obs = self.local.reset_tensors()
         z = torch.zeros(self.n_local, device=self.device)
         out = self._gather(obs, z, z.to(torch.uint8), z.to(torch.uint8), torch.full_like(obs, float("nan")) if self.with_terminal else None)

@@ -22,6 +22,9 @@ Normalization (`normalize_obs=True` / `normalize_reward=True`, `set_normalizatio
 NormalizeReward with running float64 statistics on the device; every call that returns observations or rewards returns them
 normalized (reset, step, step_torch, rollout_torch, prepare_rollout), terminal observations included.
 
+Masked reset (`reset(mask=...)`, `reset_torch(mask=...)`): only the chosen envs restart, with the episode auto-reset would
+start for them -- the loop of a training run with `auto_reset=False` (gymnasium's `reset(options={"reset_mask": ...})`).
+
 Rendering (`render=True` / `render=dict(...)`, `set_render`): `render(mode="rgb_array")` of the reference's Renderer
 (gym_space/rendering.py) for chosen envs, drawn on the device -- `render()` (NumPy) and `render_torch()` (device tensor).
 """
@@ -145,6 +148,7 @@ class SpaceGymVectorEnv:
         self._episode_stats = False
         self._render_on = False
         self._have_act = False  # a step() has filled the pinned action buffer: render() shows that action
+        self._last_obs = None  # the observations the last reset() / step() returned (reset(mask=...) keeps their other rows)
         if render:
             self.set_render(True, **(render if isinstance(render, dict) else {}))
         if episode_statistics:
@@ -381,9 +385,27 @@ class SpaceGymVectorEnv:
     def _ptr(a):
         return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
-    def reset(self):
-        self._ck(self._lib.sg_reset(self._h, self._ptr(self._obs)), "sg_reset")
+    def reset(self, mask=None):
+        """First observations of every env; with `mask` (bool or uint8 [num_envs]) only the envs whose entry is set are reset
+        (sg_reset_masked: what auto-reset would start next for each of them, the rest is left alone -- for a loop with
+        auto_reset off, gymnasium's reset(options={"reset_mask": mask})).  Returns the handle's host observation buffer (a copy
+        unless copy=False) with the masked rows replaced; its other rows are what the last reset() / step() returned."""
+        if mask is None:
+            self._ck(self._lib.sg_reset(self._h, self._ptr(self._obs)), "sg_reset")
+        else:
+            m = self._mask_host(mask)
+            if self._last_obs is not None and self._last_obs is not self._obs:
+                np.copyto(self._obs, self._last_obs)
+            self._ck(self._lib.sg_reset_masked(self._h, self._ptr(m), self._ptr(self._obs)), "sg_reset_masked")
+        self._last_obs = self._obs
         return self._obs.copy() if self.copy else self._obs
+
+    def _mask_host(self, mask):
+        """reset(mask=...): a bool or uint8 array of shape [num_envs], as contiguous uint8"""
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.bool_, np.uint8) or mask.shape != (self.num_envs,):
+            raise ValueError(f"mask: expected bool or uint8 of shape ({self.num_envs},), got {mask.dtype} {mask.shape}")
+        return np.ascontiguousarray(mask).view(np.uint8)
 
     def _check_actions(self, actions):
         if self.discrete:  # int index per env, spaceship_env.py:189-202
@@ -443,6 +465,7 @@ class SpaceGymVectorEnv:
         self._pending = False  # (the native side has given the step up as well if the wait failed)
         self._ck(rc, "sg_step_end")
         obs, rew, done, trunc, tobs = self._block_views([x.value for x in p])
+        self._last_obs = obs
         info = StepInfo({"TimeLimit.truncated": trunc.view(np.bool_) if not self.copy else trunc.astype(bool)})
         if tobs is not None:
             info["terminal_observation"] = tobs.copy() if self.copy else tobs
@@ -508,12 +531,23 @@ class SpaceGymVectorEnv:
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def reset_torch(self, out=None):
+    def reset_torch(self, out=None, mask=None):
+        """First observations of every env into `out` (default: the env's own obs tensor, the one step_torch writes by default).
+        mask: bool or uint8 CUDA tensor [num_envs] on the env's device -- only the envs whose entry is set are reset
+        (sg_reset_masked_device, no host synchronisation, graph-capturable) and only their rows of `out` are written: pass the
+        tensor step_torch filled and it holds the whole batch's observations afterwards."""
         torch, bufs = self._torch()
         obs = bufs["obs"] if out is None else out
         if out is not None:
             self._check_tensor("out", out, torch.float32, (self.num_envs, self.obs_dim))
-        self._ck(self._lib.sg_reset_device(self._h, C.c_void_p(obs.data_ptr()), self._stream()), "sg_reset_device")
+        if mask is None:
+            self._ck(self._lib.sg_reset_device(self._h, C.c_void_p(obs.data_ptr()), self._stream()), "sg_reset_device")
+            return obs
+        if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)  # (same bytes: no copy)
+        self._check_tensor("mask", mask, torch.uint8, (self.num_envs,))
+        self._ck(self._lib.sg_reset_masked_device(self._h, C.c_void_p(mask.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()),
+                 "sg_reset_masked_device")
         return obs
 
     def step_torch(self, actions, out=None, terminal_obs=None, episodes=None):

@@ -303,13 +303,11 @@ def test_fused_rollout_kernels_kepler(kernel, monkeypatch):
 
 
 @pytest.mark.parametrize("kernel", ["single", "pair"])
-@pytest.mark.parametrize("depth", ["2", "3"])
-def test_fused_rollout_kernels_and_queue_depths(kernel, depth, monkeypatch):
-    """both rollout kernels (one wave per 64 envs | pilot + finisher wave pairs; the engine picks by grid size) and both
-    depths of the episode queue give the same bits as the step kernel, with episodes of at most 40 steps (3 % of the envs
-    restart per step)"""
+def test_fused_rollout_kernels_and_queue_depths(kernel, monkeypatch):
+    """both rollout kernels (one wave per 64 envs | pilot + finisher wave pairs; the engine picks by grid size), with their
+    episode queues, give the same bits as the step kernel, with episodes of at most 40 steps (3 % of the envs restart per
+    step)"""
     monkeypatch.setenv("SPACEGYM_ROLLOUT_KERNEL", kernel)
-    monkeypatch.setenv("SPACEGYM_SPARE_DEPTH", depth)
     _fused_vs_step_by_step("GoalContinuous4P-v0", max_episode_steps=40)
 
 

@@ -354,6 +354,46 @@ int sg_render_device(sg_env *env, int32_t n, const int32_t *env_ids_dev, const v
                      uint8_t *frames_dev, void *hip_stream);
 int sg_render(sg_env *env, int32_t n, const int32_t *env_ids_host, const void *actions_host, int32_t size, uint8_t *frames_host);
 
+/* Reward profiles: different reward coefficients for different envs of one batch (reward-shaping sweeps, population-based
+ * training, curricula, reward-weight randomization).  A profile is a set of values for the reference's reward-only constructor
+ * keywords: Goal ids survival_reward_scale, goal_vel_reward_scale, safety_reward_scale, goal_sparse_reward, danger_zone
+ * (goal.py:147-158,204-227); Kepler ids numerator_C, rad_penalty_C, act_penalty_C (kepler.py:111-150).  A field left NaN takes
+ * the handle's own value; a keyword of the other family or an invalid value is refused with sg_create_ex's message.  Each
+ * profile's derived constants are those of sg_create_ex with its keywords, so env i under profile p gives bit for bit what env
+ * i of a handle created with p's keywords gives: the physics, resets, RNG and `done` do not depend on the profile.
+ * A handle holds up to 256 profiles and one uint8 profile index per env (all 0 when switched on).  An index change applies
+ * from the next env-step's reward, also in mid-episode (a curriculum that wants episode boundaries selects with `done` on the
+ * device).  sg_reset, sg_seed and masked reset keep table and indices.  Episode statistics, counters and normalization see the
+ * profiled rewards; rendering and sg_vector_field do not depend on them.  Every step entry point runs profiled step kernels,
+ * sg_rollout_device* the profiled wave-pair K-step kernels.  Off by default: then
+ * nothing is allocated or launched for them.  Snapshots taken while they are on carry table and indices (sg_save_state).
+ * The multi-device Python front ends do not serve them. */
+typedef struct sg_reward_profile {
+    uint32_t struct_size;          /* sizeof(sg_reward_profile), set by sg_reward_profile_init */
+    double survival_reward_scale;  /* Goal */
+    double goal_vel_reward_scale;
+    double safety_reward_scale;
+    double goal_sparse_reward;
+    double danger_zone;
+    double numerator_C;            /* Kepler */
+    double rad_penalty_C;
+    double act_penalty_C;
+} sg_reward_profile;
+/* every field NaN: the handle's own values */
+void sg_reward_profile_init(sg_reward_profile *p);
+/* n = 0 (profiles NULL): off, frees table and indices.  1 <= n <= 256: uploads the table (waits for the handle's work).  Indices
+ * are kept while profiles stay on; a table shorter than an index in use is refused. */
+int sg_set_reward_profiles(sg_env *env, int32_t n, const sg_reward_profile *profiles);
+/* *n = number of profiles (0: off); out (NULL to skip, else n entries) receives the effective values of every field of the
+ * handle's family (the other family's stay NaN). */
+int sg_get_reward_profiles(sg_env *env, int32_t *n, sg_reward_profile *out, int32_t capacity);
+/* The env's profile index, uint8 [num_envs].  The host form refuses an index >= n.  The device form enqueues one kernel on the
+ * stream and allocates and synchronizes nothing (hipGraph-capturable); an index >= n makes that env use profile 0 and sets the
+ * handle's status word, which sg_check_status reports (SG_ERR_INVALID) and clears.  Both fail while profiles are off. */
+int sg_set_env_profiles(sg_env *env, const uint8_t *idx_host);
+int sg_set_env_profiles_device(sg_env *env, const uint8_t *idx_dev, void *hip_stream);
+int sg_get_env_profiles(sg_env *env, uint8_t *idx_host);
+
 /* On-device action source for sg_rollout_device: the uniformly random policy (what the reference's README loop and the
  * benchmark use: env.action_space.sample(), gym spaces Box / Discrete).  Fills actions_dev [n_steps, num_envs, 2] float32
  * with i.i.d. U(-1, 1) values (discrete ids: int32 [n_steps, num_envs] uniform in 0..5).  Entry (t, i) is a function of
@@ -381,7 +421,9 @@ int sg_set_state(sg_env *env, const float *ship, const float *planets, const flo
  * (episode statistics, normalization), then those blocks: the configuration, the running statistics and `returns`.  Loading it
  * switches normalization on with that configuration and resumes it bit-identically; loading a version-1 / 2 blob into a
  * handle with normalization on starts its statistics afresh and keeps the configuration.  With normalization off the blob is
- * byte for byte what it was before normalization existed. */
+ * byte for byte what it was before normalization existed.  While reward profiles are on the blob is version 3 with one more
+ * block (the profiles as given and every env's index); loading it switches them on with that table and those indices, loading
+ * one without them leaves a handle's profiles as they are. */
 size_t sg_state_bytes(const sg_env *env);
 int sg_save_state(sg_env *env, void *blob_host, size_t bytes);
 int sg_load_state(sg_env *env, const void *blob_host, size_t bytes);

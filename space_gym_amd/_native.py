@@ -48,6 +48,14 @@ class SgRenderConfig(C.Structure):
                 ("trace_decay", C.c_double)]
 
 
+class SgRewardProfile(C.Structure):
+    """sg_reward_profile (include/spacegym.h): values of the reward-only constructor kwargs of one reward profile; NaN keeps the
+    handle's own value"""
+    _fields_ = [("struct_size", C.c_uint32), ("survival_reward_scale", C.c_double), ("goal_vel_reward_scale", C.c_double),
+                ("safety_reward_scale", C.c_double), ("goal_sparse_reward", C.c_double), ("danger_zone", C.c_double),
+                ("numerator_C", C.c_double), ("rad_penalty_C", C.c_double), ("act_penalty_C", C.c_double)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -100,6 +108,12 @@ SYMBOLS = {
     "sg_set_render": (C.c_int, [_vp, C.POINTER(SgRenderConfig)]),
     "sg_render_device": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "sg_render": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),
+    "sg_reward_profile_init": (None, [C.POINTER(SgRewardProfile)]),
+    "sg_set_reward_profiles": (C.c_int, [_vp, C.c_int32, C.POINTER(SgRewardProfile)]),
+    "sg_get_reward_profiles": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(SgRewardProfile), C.c_int32]),
+    "sg_set_env_profiles": (C.c_int, [_vp, _vp]),
+    "sg_set_env_profiles_device": (C.c_int, [_vp, _vp, _vp]),
+    "sg_get_env_profiles": (C.c_int, [_vp, _vp]),
     "sg_check_status": (C.c_int, [_vp]),
     "sg_set_counters": (C.c_int, [_vp, C.c_int32]),
     "sg_get_counters": (C.c_int, [_vp, C.POINTER(SgCounters), C.c_int32]),

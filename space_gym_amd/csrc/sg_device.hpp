@@ -1522,6 +1522,35 @@ SG_FN KeplerStepConsts kepler_step_consts(const SgDev &c) {
     return k;
 }
 
+// Reward profiles (sg_set_reward_profiles): the reward-only fields of a parameter block, one table entry per profile, made on
+// the host by apply_params on a copy of the handle's block -- the same doubles a handle created with the profile's keywords holds.
+struct GoalRewardProfile {
+    double danger_r2, survival, goal_scale, safety_scale, sparse;
+};
+struct KeplerRewardProfile {
+    double k_C, k_Cr;
+    float k_Ca;
+};
+// What goal_reward / kepler_reward read: the handle's fields that no profile sets, and the env's profile
+struct GoalRewardView {
+    double goal_r2, danger_r2, survival, goal_scale, safety_scale, sparse;
+};
+SG_FN GoalRewardView goal_reward_view(const SgDev &c, const GoalRewardProfile &p) {
+    GoalRewardView v;
+    v.goal_r2 = c.goal_r2; v.danger_r2 = p.danger_r2; v.survival = p.survival; v.goal_scale = p.goal_scale;
+    v.safety_scale = p.safety_scale; v.sparse = p.sparse;
+    return v;
+}
+struct KeplerRewardView {
+    double k_gm, k_C, k_Cr;
+    float k_Ca;
+};
+SG_FN KeplerRewardView kepler_reward_view(const SgDev &c, const KeplerRewardProfile &p) {
+    KeplerRewardView v;
+    v.k_gm = c.k_gm; v.k_C = p.k_C; v.k_Cr = p.k_Cr; v.k_Ca = p.k_Ca;
+    return v;
+}
+
 // The same from a by-value copy of the few parameters it needs: a K-step loop keeps them in registers instead of re-reading
 // the parameter block every step.
 struct StepConsts {
@@ -1550,6 +1579,21 @@ SG_FN void goal_env_begin(const StepConsts &k, const GoalEnv<N> &e, float a0, fl
     I.begin(k.h, k.half_world, k.gm, F, om0, alpha, k.omega_limit, e.x, e.y, e.th, e.vx, e.vy, e.px, e.py, cR, cRd, use_probe);
 }
 
+// (RC: what goal_reward reads -- the parameter block, or a GoalRewardView of the env's reward profile.  goal_env_finish below
+//  repeats this body instead of calling it with (c, c): called that way, the one-wave Goal step kernels without profiles
+//  compiled to other instructions -- two independent instructions of the integration swapped -- and they are to stay as they
+//  were.  Keep the two in step.)
+template <int N, typename RC>
+SG_FN void goal_env_finish_r(const SgDev &c, const RC &rc, GoalEnv<N> &e, const StepResult &r, float (&obs)[7 + 2 * N + 2],
+                             float &reward, int &done, int &hit) {
+    SG_STAMP(11);
+    reward = goal_reward<N>(rc, e.x, e.y, r.dXd, r.dYd, e.px, e.py, e.gx, e.gy, hit);
+    SG_STAMP(12);
+    e.x = (float)((double)e.x + r.dXd); e.y = (float)((double)e.y + r.dYd); e.vx = r.vx; e.vy = r.vy; e.om = r.om;
+    e.th = wrap_two_pi(e.th + r.dth);
+    done = r.done;
+    goal_observe<N>(c, e, obs);
+}
 template <int N>
 SG_FN void goal_env_finish(const SgDev &c, GoalEnv<N> &e, const StepResult &r, float (&obs)[7 + 2 * N + 2],
                            float &reward, int &done, int &hit) {
@@ -1596,9 +1640,10 @@ SG_FN Orbit fixed_orbit(const SgDev &c) {
     return ob;
 }
 
-template <bool ACCEL = false>
-SG_FN void kepler_env_step(const SgDev &c, const Orbit &ob, KeplerEnv &e, float a0, float a1, float (&obs)[10],
-                           float &reward, int &done, StepResult &r, bool use_probe = true) {
+// (RC: what kepler_reward reads -- the parameter block, or a KeplerRewardView of the env's reward profile)
+template <bool ACCEL, typename RC>
+SG_FN void kepler_env_step_r(const SgDev &c, const RC &rc, const Orbit &ob, KeplerEnv &e, float a0, float a1, float (&obs)[10],
+                             float &reward, int &done, StepResult &r, bool use_probe) {
     float engine, F, om, om0, alpha;
     translate_action(a0, a1, c.max_engine_force, engine, F, om);
     steering<ACCEL>(c, a1, om, e.om, om0, alpha);
@@ -1608,11 +1653,16 @@ SG_FN void kepler_env_step(const SgDev &c, const Orbit &ob, KeplerEnv &e, float 
     const double cRd[2] = {c.planet_r_d, (double)c.border_r};
     make_step<2, 1, false, ACCEL>(c.h, c.half_world, c.gm, F, om0, alpha, c.omega_limit, e.x, e.y, e.th, e.vx, e.vy, cax, cay,
                                   cR, cRd, r, use_probe);
-    reward = kepler_reward(c, ob, e.x, e.y, r.dXd, r.dYd, r.vx, r.vy, engine, a1);
+    reward = kepler_reward(rc, ob, e.x, e.y, r.dXd, r.dYd, r.vx, r.vy, engine, a1);
     e.x = (float)((double)e.x + r.dXd); e.y = (float)((double)e.y + r.dYd); e.vx = r.vx; e.vy = r.vy; e.om = r.om;
     e.th = wrap_two_pi(e.th + r.dth);
     done = r.done;
     kepler_observe(c, e, obs);
+}
+template <bool ACCEL = false>
+SG_FN void kepler_env_step(const SgDev &c, const Orbit &ob, KeplerEnv &e, float a0, float a1, float (&obs)[10],
+                           float &reward, int &done, StepResult &r, bool use_probe = true) {
+    kepler_env_step_r<ACCEL>(c, c, ob, e, a0, a1, obs, reward, done, r, use_probe);
 }
 
 }  // namespace sg

@@ -22,7 +22,7 @@ class MultiDeviceVectorEnv:
     def __init__(self, env_id, num_envs, devices, seed=0, env_index_base=0, copy=True, **kwargs):
         """devices: GPU indices, one block of envs each (the first is the root: where actions are taken from and results
         land); an index may repeat (several blocks on one GPU: how the tests run it on a one-GPU box).  kwargs: make_vec's,
-        except episode_statistics, the normalization keywords and render: the per-device blocks do not gather episode statistics
+        except episode_statistics, the normalization keywords, render and reward_profiles: the per-device blocks do not gather episode statistics
         or frames yet, and running statistics over all blocks need a cross-device reduction."""
         import torch
         self._torch = torch
@@ -38,6 +38,8 @@ class MultiDeviceVectorEnv:
         engine.pop("device", None)
         if engine.pop("render", False):
             raise NotImplementedError("render: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device renders its envs)")
+        if engine.pop("reward_profiles", None):
+            raise NotImplementedError("reward_profiles: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device has them)")
         if engine.pop("episode_statistics", False):
             raise NotImplementedError("episode_statistics: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device has them)")
         norm = {k: engine.pop(k) for k in _NORM_KWARGS if k in engine}

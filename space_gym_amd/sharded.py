@@ -40,6 +40,8 @@ class ShardedVectorEnv:
         see the module docstring."""
         if kwargs.get("render"):
             raise NotImplementedError("render: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv renders its envs)")
+        if kwargs.get("reward_profiles"):
+            raise NotImplementedError("reward_profiles: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv has them)")
         if kwargs.get("episode_statistics"):
             raise NotImplementedError("episode_statistics: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv has them)")
         norm = {k: kwargs.pop(k) for k in ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs",

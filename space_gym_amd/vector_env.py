@@ -53,6 +53,15 @@ RENDER_SIZES = (16, 2048)
 RENDER_CAPACITY = 16
 
 
+# reward profiles: the most a handle holds, and the reward-only constructor keywords a profile sets (goal.py:147-158,204-227;
+# kepler.py:111-150).  Physics keywords are not profile keywords.
+REWARD_PROFILES_MAX = 256
+REWARD_KWARGS = {"goal": ("survival_reward_scale", "goal_vel_reward_scale", "safety_reward_scale", "goal_sparse_reward", "danger_zone"),
+                 "kepler": ("numerator_C", "rad_penalty_C", "act_penalty_C")}
+_PHYSICS_KWARGS = ("max_engine_force", "ship_moi", "step_size", "n_planets", "ref_orbit_a", "ref_orbit_eccentricity", "ref_orbit_angle",
+                   "randomize", "ship_steering")
+
+
 def render_config(family, capacity=RENDER_CAPACITY, trace_len=None, trace_decay=None, debug_lidar=None):
     """Checks set_render's keywords and returns them as the native config takes them (-1 / NaN: the family's value).
     family: "goal" or "kepler"."""
@@ -84,7 +93,7 @@ class SpaceGymVectorEnv:
     def __init__(self, env_id, num_envs, device=0, seed=0, env_index_base=0, max_episode_steps=None, auto_reset=True,
                  validate_actions=True, terminal_observation=True, copy=True, steering=None, env_kwargs=None, from_class=False,
                  episode_statistics=False, normalize_obs=False, normalize_reward=False, norm_gamma=0.99, norm_epsilon=1e-8,
-                 clip_obs=None, clip_reward=None, render=False, _handle=None):
+                 clip_obs=None, clip_reward=None, render=False, reward_profiles=None, _handle=None):
         """steering: "velocity" (ship_steering=1, what every registered id uses) or "acceleration" (ship_steering=0, the
         constructor default of the reference classes: omega is a state, the thruster a torque); None: what env_kwargs say.
         env_kwargs: keyword arguments of the reference's constructor (GoalEnv.__init__ goal.py:18-31, KeplerEnv.__init__
@@ -99,7 +108,8 @@ class SpaceGymVectorEnv:
         episode_statistics: switch the episode statistics on from the start (set_episode_statistics).
         normalize_obs / normalize_reward, norm_gamma, norm_epsilon, clip_obs, clip_reward: switch normalization on from the start
         (set_normalization).
-        render: True or a dict of set_render's keywords (capacity, trace_len, trace_decay, debug_lidar): switch rendering on."""
+        render: True or a dict of set_render's keywords (capacity, trace_len, trace_decay, debug_lidar): switch rendering on.
+        reward_profiles: a list of dicts of reward keywords: switch reward profiles on from the start (set_reward_profiles)."""
         if env_id not in ENV_SPECS:
             raise ValueError(f"unknown env id {env_id!r}; served ids: {sorted(ENV_SPECS)}")
         self._lib = _native.load()
@@ -156,6 +166,8 @@ class SpaceGymVectorEnv:
         if normalize_obs or normalize_reward:
             self.set_normalization(obs=normalize_obs, reward=normalize_reward, gamma=norm_gamma, epsilon=norm_epsilon,
                                    clip_obs=clip_obs, clip_reward=clip_reward)
+        if reward_profiles is not None:
+            self.set_reward_profiles(reward_profiles)
 
     def _native_params(self, kw):
         """sg_params (include/spacegym.h) from the constructor's keyword arguments"""
@@ -303,6 +315,77 @@ class SpaceGymVectorEnv:
             else:
                 args.append(None)
         self._ck(self._lib.sg_set_normalize_state(self._h, *[self._ptr(a) for a in args]), "sg_set_normalize_state")
+
+    # ------------------------------------------------------------------ reward profiles
+    def set_reward_profiles(self, profiles):
+        """Different reward coefficients for different envs of the batch (sg_set_reward_profiles).  profiles: a list of at most
+        256 dicts of the reference's reward-only constructor keywords -- Goal ids survival_reward_scale, goal_vel_reward_scale,
+        safety_reward_scale, goal_sparse_reward, danger_zone; Kepler ids numerator_C, rad_penalty_C, act_penalty_C; a keyword
+        left out keeps the env's own value.  Env i under profile p gives bit for bit what env i of make_vec(..., **p) gives.
+        Every env starts at profile 0 (set_env_profiles chooses); the indices are kept while profiles stay on.  None or []:
+        off."""
+        if self._pending:
+            raise RuntimeError("set_reward_profiles() while a step is in flight (step_wait() first)")
+        profiles = [] if profiles is None else list(profiles)
+        if len(profiles) > REWARD_PROFILES_MAX:
+            raise ValueError(f"reward profiles: at most {REWARD_PROFILES_MAX}, got {len(profiles)}")
+        arr = (_native.SgRewardProfile * max(1, len(profiles)))()
+        for k, prof in enumerate(profiles):
+            if not isinstance(prof, dict):
+                raise TypeError(f"reward profile {k}: a dict of reward keywords, got {type(prof).__name__}")
+            self._lib.sg_reward_profile_init(C.byref(arr[k]))
+            for name, v in prof.items():
+                if name not in REWARD_KWARGS["goal"] + REWARD_KWARGS["kepler"]:
+                    what = "a physics keyword: reward profiles set reward keywords only" if name in _PHYSICS_KWARGS else "unknown keyword"
+                    raise ValueError(f"reward profile {k}: {name!r}: {what} ({', '.join(REWARD_KWARGS[self.spec['family']])})")
+                if v is None:
+                    continue
+                setattr(arr[k], name, float(v))  # (the other family's keywords are refused by the library, as sg_create_ex does)
+        self._ck(self._lib.sg_set_reward_profiles(self._h, len(profiles), arr if profiles else None), "sg_set_reward_profiles")
+
+    def reward_profiles(self):
+        """the effective profiles (sg_get_reward_profiles): a list of dicts of the family's reward keywords; [] while off"""
+        n = C.c_int32()
+        self._ck(self._lib.sg_get_reward_profiles(self._h, C.byref(n), None, 0), "sg_get_reward_profiles")
+        if not n.value:
+            return []
+        arr = (_native.SgRewardProfile * n.value)()
+        self._ck(self._lib.sg_get_reward_profiles(self._h, C.byref(n), arr, n.value), "sg_get_reward_profiles")
+        return [{k: getattr(p, k) for k in REWARD_KWARGS[self.spec["family"]]} for p in arr]
+
+    def set_env_profiles(self, idx):
+        """Each env's reward profile, from the next env-step's reward on (also in mid-episode; a curriculum that changes profiles
+        at episode boundaries only selects on the device: torch.where(done, new, idx)).  idx: integers of shape [num_envs] (NumPy
+        or any array-like; refused if one is past the table), or a uint8 CUDA tensor on the env's device -- then one kernel on
+        torch's current stream copies it, with no host synchronisation (graph-capturable); an index past the table makes that
+        env use profile 0 and is reported by check_status()."""
+        try:
+            import torch
+        except ImportError:
+            torch = None
+        if torch is not None and isinstance(idx, torch.Tensor) and idx.is_cuda:
+            self._check_tensor("idx", idx, torch.uint8, (self.num_envs,))
+            self._ck(self._lib.sg_set_env_profiles_device(self._h, C.c_void_p(idx.data_ptr()), self._stream()),
+                     "sg_set_env_profiles_device")
+            return
+        a = np.asarray(idx.cpu() if torch is not None and isinstance(idx, torch.Tensor) else idx)
+        if a.shape != (self.num_envs,):
+            raise ValueError(f"idx: expected shape ({self.num_envs},), got {a.shape}")
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"idx: expected integers, got {a.dtype}")
+        n = len(self.reward_profiles())
+        if not n:
+            raise ValueError("set_env_profiles: reward profiles are off (set_reward_profiles first)")
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise ValueError(f"idx: profile indices must be in [0, {n}), got [{a.min()}, {a.max()}]")
+        a = np.ascontiguousarray(a, np.uint8)
+        self._ck(self._lib.sg_set_env_profiles(self._h, self._ptr(a)), "sg_set_env_profiles")
+
+    def env_profiles(self):
+        """each env's reward profile index, uint8 [num_envs] (waits for the enqueued work)"""
+        out = np.empty(self.num_envs, np.uint8)
+        self._ck(self._lib.sg_get_env_profiles(self._h, self._ptr(out)), "sg_get_env_profiles")
+        return out
 
     # ------------------------------------------------------------------ rendering
     def set_render(self, on=True, capacity=RENDER_CAPACITY, trace_len=None, trace_decay=None, debug_lidar=None):
@@ -822,7 +905,7 @@ class SpaceGymVectorEnv:
 
 _ENGINE_KWARGS = ("device", "seed", "env_index_base", "max_episode_steps", "auto_reset", "validate_actions", "terminal_observation",
                   "copy", "steering", "env_kwargs", "from_class", "episode_statistics", "normalize_obs", "normalize_reward",
-                  "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward", "render")
+                  "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward", "render", "reward_profiles")
 # the normalization keywords, which the multi-device front ends do not serve yet (a cross-device reduction is needed)
 _NORM_KWARGS = ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
 

@@ -428,6 +428,38 @@ size_t sg_state_bytes(const sg_env *env);
 int sg_save_state(sg_env *env, void *blob_host, size_t bytes);
 int sg_load_state(sg_env *env, const void *blob_host, size_t bytes);
 
+/* Device-resident snapshots: the per-env data of a handle in a buffer of the caller's in device memory (16-byte aligned, at
+ * least sg_snapshot_bytes(env) bytes for the handle as it is configured now), for rollback, search and branching inside the
+ * training loop (the reference: copy.deepcopy(env)).  Both calls enqueue on the caller's stream, allocate nothing, never
+ * synchronise and are hipGraph-capturable; any number of snapshots of one handle can exist at once.
+ * A snapshot holds: a 32-byte header written by the snapshot kernel (magic, family, n_planets, randomize_orbit, num_envs, a
+ * flags word naming the optional blocks), then the per-env columns of the blob above (q0, q1, ctr, aux, pl0, pl1, cshift, orbd, as
+ * the id has them); with episode statistics on the running return (float64) and length (int32) of every env; with
+ * normalization on `returns` (float64).  Every block starts 16-byte aligned.  It does NOT hold the seed, the normalizer's
+ * running mean / var / count, the reward-profile table or the per-env profile index: those are configuration and learning
+ * state of the handle and stay as they are on restore (a restored env keeps the profile of its slot; copy the index with
+ * sg_set_env_profiles[_device] for the other behaviour).
+ * sg_restore_device: for every env i with mask_dev[i] != 0 (NULL: every env), with j = src_dev[i] (NULL: j = i), env i's
+ * columns (and running episode statistics / returns when on) become those of the snapshot's env j; its episode queue is
+ * emptied; with rendering on the traces of ALL slots start afresh at the next render call (also when a captured restore is
+ * replayed); if obs_dev [num_envs, obs_dim] is given, row i becomes the observation of the restored state (normalized and
+ * clipped with the statistics as they are when observation normalization is on; the statistics are not updated).  Nothing of
+ * the other envs is written.  Episode counters are part of the state: done / truncated come out as they would have after the
+ * snapshot; sg_get_counters totals are not rewound.  No RNG state is copied (the RNG is keyed by seed, global env index,
+ * episode, block, stream): with j = i and the seed unchanged everything after the restore is bit-identical to what followed the
+ * snapshot under the same actions; with j != i env i continues j's trajectory bit for bit until its next random draw (goal hit
+ * or reset), which comes from its own stream -- what sg_load_state does with a blob whose columns were gathered on the host.
+ * Duplicate sources are allowed.  A buffer that overlaps the handle's own memory is the caller's error.
+ * Refused on the host (SG_ERR_INVALID, nothing enqueued): a null or misaligned buffer, bytes < sg_snapshot_bytes, a handle not
+ * reset since sg_create / sg_seed, a step in flight.  Checked on the device, before anything is written: a header that does
+ * not match the handle (other family, planets, batch size or blocks) restores nothing; a src_dev[i] outside [0, num_envs)
+ * leaves env i as it is.  Both set the handle's status word: every later call on the handle fails with SG_ERR_HIP until
+ * sg_check_status has reported the condition (SG_ERR_INVALID) and cleared it. */
+size_t sg_snapshot_bytes(const sg_env *env);
+int sg_snapshot_device(sg_env *env, void *snap_dev, size_t bytes, void *hip_stream);
+int sg_restore_device(sg_env *env, const void *snap_dev, size_t bytes, const uint8_t *mask_dev, const int32_t *src_dev,
+                      float *obs_dev, void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

@@ -120,6 +120,9 @@ SYMBOLS = {
     "sg_state_bytes": (C.c_size_t, [_vp]),
     "sg_save_state": (C.c_int, [_vp, _vp, C.c_size_t]),
     "sg_load_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "sg_snapshot_bytes": (C.c_size_t, [_vp]),
+    "sg_snapshot_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    "sg_restore_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -128,6 +128,12 @@ class MultiDeviceVectorEnv:
         self._fan_out(work)
         return obs.clone() if self.copy else obs
 
+    def _no_snapshots(self, *args, **kwargs):
+        raise NotImplementedError("snapshot / restore: not served by MultiDeviceVectorEnv (one SpaceGymVectorEnv per device snapshots "
+                                  "and restores its envs)")
+
+    snapshot = snapshot_torch = restore = restore_torch = _no_snapshots
+
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)
         for all envs on the root device.  copy=False: the front end's own arrays, two sets that alternate (what a call returns

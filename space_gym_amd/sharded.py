@@ -128,6 +128,12 @@ class ShardedVectorEnv:
         out = self._gather(obs, z, z.to(torch.uint8), z.to(torch.uint8), torch.full_like(obs, float("nan")) if self.with_terminal else None)
         return out[0] if out is not None else None
 
+    def _no_snapshots(self, *args, **kwargs):
+        raise NotImplementedError("snapshot / restore: not served by ShardedVectorEnv (a rank's SpaceGymVectorEnv snapshots and restores "
+                                  "its envs)")
+
+    snapshot = snapshot_torch = restore = restore_torch = _no_snapshots
+
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""
         tail = () if self.discrete else (2,)

@@ -794,7 +794,8 @@ class SpaceGymVectorEnv:
         return se[order, 0], se[order, 1], ob[order]
 
     def check_status(self):
-        """waits for the enqueued work; raises if a rollout kernel's bounded wave hand-off wait ran out (sg_check_status)"""
+        """waits for the enqueued work; raises if a rollout kernel's bounded wave hand-off wait ran out, or a device-side call
+        refused its input (render id, profile index, a restore's snapshot or source index) since the last call (sg_check_status)"""
         self._ck(self._lib.sg_check_status(self._h), "sg_check_status")
 
     # ------------------------------------------------------------------ complete snapshot
@@ -871,6 +872,84 @@ class SpaceGymVectorEnv:
         assert off == blob.size, (off, blob.size)
         return out
 
+    # ------------------------------------------------------------------ device-resident snapshots
+    def snapshot_torch(self, out=None):
+        """The per-env data of the handle (state columns, running episode statistics and normalizer returns when on) copied into
+        a buffer in device memory on torch's current stream (sg_snapshot_device: one launch, no host synchronisation,
+        graph-capturable).  Returns a DeviceSnapshot; out= (an earlier one of this env) reuses its buffer.  Not in a snapshot: the
+        seed, the normalizer's running statistics, the reward profiles and every env's profile index."""
+        import torch
+        n = int(self._lib.sg_snapshot_bytes(self._h))
+        if out is None:
+            out = DeviceSnapshot(torch.empty(n, dtype=torch.uint8, device=f"cuda:{self.device}"), self.num_envs, self.env_id)
+        self._check_snapshot("out", out, n)
+        self._ck(self._lib.sg_snapshot_device(self._h, C.c_void_p(out.buffer.data_ptr()), C.c_size_t(n), self._stream()),
+                 "sg_snapshot_device")
+        return out
+
+    def _check_snapshot(self, name, snap, n):
+        if not isinstance(snap, DeviceSnapshot):
+            raise ValueError(f"{name}: expected a DeviceSnapshot (snapshot_torch), got {type(snap).__name__}")
+        if snap.num_envs != self.num_envs or snap.env_id != self.env_id:
+            raise ValueError(f"{name}: a snapshot of {snap.num_envs} envs of {snap.env_id}, this env has {self.num_envs} of {self.env_id}")
+        import torch
+        buf = snap.buffer
+        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.device.index == self.device):
+            raise ValueError(f"{name}.buffer: expected a CUDA tensor on device {self.device}")
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() < n or not buf.is_contiguous():
+            raise ValueError(f"{name}.buffer: expected contiguous uint8 of at least {n} bytes (has the env's configuration -- episode "
+                             f"statistics, normalization -- changed since the snapshot?), got {buf.dtype} {tuple(buf.shape)}")
+
+    def restore_torch(self, snap, mask=None, src=None, out=None):
+        """Env i with mask[i] set (mask None: every env) takes the state of the snapshot's env src[i] (src None: i) on torch's
+        current stream (sg_restore_device: no host synchronisation, graph-capturable).  mask: bool or uint8 CUDA tensor
+        [num_envs]; src: int32 CUDA tensor [num_envs] (duplicates allowed; an index outside the batch leaves its env as it is
+        and check_status() raises).  Only the restored envs' rows of `out` (default: the env's own obs tensor, as reset_torch)
+        are written: the observation of the restored state, normalized with the statistics as they are -- which a restore does
+        not update.  With rendering on every trace starts afresh.  Returns the obs tensor."""
+        torch, bufs = self._torch()
+        self._check_snapshot("snap", snap, int(self._lib.sg_snapshot_bytes(self._h)))
+        obs = bufs["obs"] if out is None else out
+        if out is not None:
+            self._check_tensor("out", out, torch.float32, (self.num_envs, self.obs_dim))
+        if mask is not None:
+            if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)  # (same bytes: no copy)
+            self._check_tensor("mask", mask, torch.uint8, (self.num_envs,))
+        if src is not None:
+            self._check_tensor("src", src, torch.int32, (self.num_envs,))
+        self._ck(self._lib.sg_restore_device(self._h, C.c_void_p(snap.buffer.data_ptr()), C.c_size_t(snap.buffer.numel()),
+                                             C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                             C.c_void_p(src.data_ptr()) if src is not None else None,
+                                             C.c_void_p(obs.data_ptr()), self._stream()), "sg_restore_device")
+        return obs
+
+    def snapshot(self):
+        """NumPy-path convenience: snapshot_torch() after the work enqueued so far (the snapshot itself stays on the device)"""
+        import torch
+        snap = self.snapshot_torch()
+        torch.cuda.current_stream(self.device).synchronize()
+        return snap
+
+    def restore(self, snap, mask=None, src=None):
+        """NumPy-path convenience over restore_torch: mask (bool or uint8 [num_envs]) and src (integers [num_envs]) are host
+        arrays; returns the host observation block the way reset(mask=...) does -- the restored envs' rows replaced, the other
+        rows what the last reset() / step() returned."""
+        import torch
+        dev = f"cuda:{self.device}"
+        m = torch.from_numpy(self._mask_host(mask).copy()).to(dev) if mask is not None else None
+        if src is not None:
+            src = np.asarray(src)
+            if src.dtype.kind not in "iu" or src.shape != (self.num_envs,):
+                raise ValueError(f"src: expected integers of shape ({self.num_envs},), got {src.dtype} {src.shape}")
+            src = torch.from_numpy(np.clip(src, -1, self.num_envs).astype(np.int32)).to(dev)  # (outside the batch stays outside)
+        last = self._last_obs if self._last_obs is not None else self._obs
+        obs = torch.from_numpy(np.ascontiguousarray(last, np.float32)).to(dev)
+        self.restore_torch(snap, mask=m, src=src, out=obs)
+        np.copyto(self._obs, obs.cpu().numpy())
+        self._last_obs = self._obs
+        return self._obs.copy() if self.copy else self._obs
+
     def random_actions_torch(self, n_steps, seed=0, first_step=0, out=None):
         """the uniformly random policy generated on the device: [n_steps, B, 2] float32 in (-1, 1) (discrete ids: int32
         [n_steps, B] in 0..5); entry (t, i) depends only on (seed, global env index, first_step + t)."""
@@ -908,6 +987,15 @@ _ENGINE_KWARGS = ("device", "seed", "env_index_base", "max_episode_steps", "auto
                   "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward", "render", "reward_profiles")
 # the normalization keywords, which the multi-device front ends do not serve yet (a cross-device reduction is needed)
 _NORM_KWARGS = ("normalize_obs", "normalize_reward", "norm_gamma", "norm_epsilon", "clip_obs", "clip_reward")
+
+
+class DeviceSnapshot:
+    """What snapshot_torch returns: `buffer` (uint8 CUDA tensor of sg_snapshot_bytes bytes, the caller's to keep, clone or
+    overwrite through snapshot_torch(out=...)), and the batch size and env id it was taken from (checked by restore_torch)."""
+    __slots__ = ("buffer", "num_envs", "env_id")
+
+    def __init__(self, buffer, num_envs, env_id):
+        self.buffer, self.num_envs, self.env_id = buffer, int(num_envs), env_id
 
 
 def make_vec(env_id, num_envs=1, **kwargs):

@@ -15,7 +15,7 @@
  *     they only enqueue kernels on the given stream (hipGraph-capturable);
  *   - the host-buffer calls (sg_reset, sg_reset_masked, sg_step, sg_get_state, sg_set_state, sg_vector_field, sg_save_state, sg_load_state,
  *     sg_seed, sg_set_auto_reset, sg_set_episode_stats, sg_step_episodes, sg_set_normalize, sg_get_normalize_state,
- *     sg_set_normalize_state, sg_render) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
+ *     sg_set_normalize_state, sg_render, sg_gae) run on the handle's own stream, wait for whatever the *_device calls have enqueued on
  *     the caller's streams before, and return when they are complete -- no manual synchronisation between the two kinds;
  *   - a handle is not thread-safe; independent handles are.
  *   - observations/rewards are float32 (the reference returns float64; parity tolerance in DESIGN.md).
@@ -459,6 +459,68 @@ size_t sg_snapshot_bytes(const sg_env *env);
 int sg_snapshot_device(sg_env *env, void *snap_dev, size_t bytes, void *hip_stream);
 int sg_restore_device(sg_env *env, const void *snap_dev, size_t bytes, const uint8_t *mask_dev, const int32_t *src_dev,
                       float *obs_dev, void *hip_stream);
+
+/* Advantages and returns of a rollout by generalized advantage estimation (Schulman et al. 2016; SB3
+ * RolloutBuffer.compute_returns_and_advantage, CleanRL's PPO) -- what an on-policy learner computes next from the rows
+ * sg_rollout_device* wrote and its value estimates.  The reference has no counterpart.  For a rollout of K = n_steps steps of
+ * B = num_envs envs, in the rollout's own layout:
+ *   reward          float32 [K, B]   as returned (raw, profiled or normalized: whatever the caller passes)
+ *   done, truncated uint8   [K, B]   as returned
+ *   value           float32 [K, B]   V of the observation action t was taken from (the obs before the rollout for t = 0, obs[t - 1]
+ *                                    after); NULL: all zero -- the advantage is then the discounted reward-to-go
+ *   last_value      float32 [B]      V of obs[K - 1]; NULL: zero
+ *   terminal values                  V of the LAST observation of the episode that ended at (t, i), in one of two forms (or neither):
+ *     dense         float32 [K, B]   read only where done and truncated are both set;
+ *     list          sg_value_list    a rollout's sg_terminal_list with the caller's V(obs[k]) beside it: the same count and
+ *                                    step_env, `value` float32 [capacity], in any order
+ *   advantage, ret  float32 [K, B]   outputs
+ * Per env i, in float64, every operation rounded on its own (no fused multiply-add), gl = gamma * lambda rounded once on the host:
+ *   A = 0
+ *   for t = K - 1 .. 0:
+ *       if done[t, i]:  nv = the terminal value of (t, i) if truncated[t, i] and bootstrap_truncated and terminal values are given,
+ *                            else 0
+ *                       A  = (reward[t, i] + gamma * nv) - value[t, i]               -- nothing crosses an episode boundary
+ *       else:           nv = value[t + 1, i], or last_value[i] for t = K - 1
+ *                       A  = ((reward[t, i] + gamma * nv) - value[t, i]) + gl * A
+ *       advantage[t, i] = (float) A;  ret[t, i] = (float) (A + value[t, i])
+ * With auto-reset on, value[t + 1] at a finished step belongs to the next episode and is never used; a truncated episode
+ * bootstraps from the value of its own last observation, which is what sg_rollout_device_terminal's list is for.  A NaN or inf
+ * inside one episode stays inside that episode.  The result depends on the arguments only: not on the handle's state or env id
+ * (the handle gives B, the device and the status word).  tests/gae_model.py is the same recurrence in NumPy, bit for bit.
+ * sg_gae_device enqueues on the caller's stream -- one kernel, or two with a list (the first scatters the list's values into
+ * `advantage`, where the second reads each one before it overwrites it: no scratch) -- allocates nothing, never synchronises, is
+ * hipGraph-capturable (one stream) and leaves every env untouched.  Pointers need only their type's alignment (rows of odd B,
+ * views into larger buffers).  Inputs must not overlap the outputs.
+ * Refused on the host (SG_ERR_INVALID, nothing enqueued): n_steps < 1; a null reward, done, truncated, advantage or ret; both
+ * terminal forms at once; gamma or lambda outside [0, 1] or NaN; a wrong struct_size.  Checked on the device: a list whose count
+ * exceeds its capacity (values are missing: those steps bootstrap from garbage) and a step_env record outside [0, K) x [0, B)
+ * (ignored) set the handle's status word: every later call on the handle fails with SG_ERR_HIP until sg_check_status has reported
+ * the condition (SG_ERR_INVALID) and cleared it.
+ * sg_gae is the same for host arrays (a list's pointers are host pointers too), on the handle's stream like the other
+ * host-buffer calls; it allocates a device block for the call and refuses a bad list up front. */
+typedef struct sg_gae_config {
+    uint32_t struct_size;         /* sizeof(sg_gae_config), set by sg_gae_config_init */
+    double gamma;                 /* discount, in [0, 1] */
+    double lambda;                /* GAE's lambda, in [0, 1] */
+    int32_t bootstrap_truncated;  /* 1: a truncated episode bootstraps from its terminal value; 0: a truncation ends the episode
+                                     like a terminal event (next value 0) and the terminal values are not read */
+} sg_gae_config;
+/* gamma 0.99, lambda 0.95, bootstrap_truncated 1 */
+void sg_gae_config_init(sg_gae_config *cfg);
+typedef struct sg_value_list {
+    const uint32_t *count;    /* [1]: records in the list (sg_terminal_list.count of the rollout) */
+    const int32_t *step_env;  /* [capacity, 2]: (step, env) of each record (sg_terminal_list.step_env) */
+    const float *value;       /* [capacity]: V of the record's terminal observation */
+    uint32_t capacity;
+} sg_value_list;
+/* cfg NULL: sg_gae_config_init's values */
+int sg_gae_device(sg_env *env, int32_t n_steps, const sg_gae_config *cfg, const float *reward_dev, const uint8_t *done_dev,
+                  const uint8_t *truncated_dev, const float *value_dev, const float *last_value_dev,
+                  const float *terminal_value_dense_dev, const sg_value_list *terminal_value_list, float *advantage_dev,
+                  float *ret_dev, void *hip_stream);
+int sg_gae(sg_env *env, int32_t n_steps, const sg_gae_config *cfg, const float *reward_host, const uint8_t *done_host,
+           const uint8_t *truncated_host, const float *value_host, const float *last_value_host,
+           const float *terminal_value_dense_host, const sg_value_list *terminal_value_list, float *advantage_host, float *ret_host);
 
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its

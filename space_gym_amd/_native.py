@@ -56,6 +56,16 @@ class SgRewardProfile(C.Structure):
                 ("numerator_C", C.c_double), ("rad_penalty_C", C.c_double), ("act_penalty_C", C.c_double)]
 
 
+class SgGaeConfig(C.Structure):
+    """sg_gae_config (include/spacegym.h): sg_gae_config_init fills in gamma 0.99, lambda 0.95, bootstrap_truncated 1"""
+    _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_double), ("lambda_", C.c_double), ("bootstrap_truncated", C.c_int32)]
+
+
+class SgValueList(C.Structure):
+    """sg_value_list (include/spacegym.h): a rollout's terminal list with the caller's values of its observations"""
+    _fields_ = [("count", C.c_void_p), ("step_env", C.c_void_p), ("value", C.c_void_p), ("capacity", C.c_uint32)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -123,6 +133,9 @@ SYMBOLS = {
     "sg_snapshot_bytes": (C.c_size_t, [_vp]),
     "sg_snapshot_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "sg_restore_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "sg_gae_config_init": (None, [C.POINTER(SgGaeConfig)]),
+    "sg_gae_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp, _vp]),
+    "sg_gae": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -950,6 +950,119 @@ class SpaceGymVectorEnv:
         self._last_obs = self._obs
         return self._obs.copy() if self.copy else self._obs
 
+    # ------------------------------------------------------------------ GAE advantages and returns of a rollout
+    @staticmethod
+    def _gae_config(gamma, lam, bootstrap_truncated):
+        gamma, lam = float(gamma), float(lam)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam must be in [0, 1], got {lam}")
+        return _native.SgGaeConfig(C.sizeof(_native.SgGaeConfig), gamma, lam, int(bool(bootstrap_truncated)))
+
+    @staticmethod
+    def value_list_torch(terminal, values):
+        """the `terminal=` argument of gae_torch from a rollout's terminal list (terminal_list_torch, filled by rollout_torch)
+        and the caller's values of its observations, V(terminal["obs"]) as float32 [capacity]"""
+        return dict(count=terminal["count"], step_env=terminal["step_env"], value=values)
+
+    def gae_torch(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
+                  bootstrap_truncated=True, out=None):
+        """Advantages and returns of a rollout by generalized advantage estimation (sg_gae_device: one launch, two with a
+        list; torch's current stream, no host synchronisation, nothing allocated by the engine, graph-capturable).
+        reward float32 / done, trunc uint8 [K, B] as rollout_torch wrote them; value float32 [K, B]: V of the observation action t
+        was taken from (None: zeros -- the advantage is the discounted reward-to-go); last_value float32 [B]: V of obs[K - 1]
+        (None: zeros).  The value of the last observation of an episode that was truncated at (t, i), to bootstrap from, comes
+        either from terminal_value (dense float32 [K, B], read only where done and trunc are both set) or from terminal, a dict
+        count / step_env / value (value_list_torch: a rollout's terminal list with V(terminal["obs"]) beside it); with neither,
+        or bootstrap_truncated=False, a truncation ends the episode like a terminal event.  out: dict advantage / returns of
+        float32 [K, B] (allocated when absent).  Returns (advantage, returns); tests/gae_model.py states the arithmetic."""
+        import torch
+        if terminal_value is not None and terminal is not None:
+            raise ValueError("terminal_value and terminal: give the terminal values in one form")
+        cfg = self._gae_config(gamma, lam, bootstrap_truncated)
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+            raise ValueError("reward: expected a CUDA tensor of shape (K, num_envs)")
+        K, B = int(reward.shape[0]), self.num_envs
+        if K < 1:
+            raise ValueError("reward: expected at least one step")
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        if value is not None:
+            self._check_tensor("value", value, torch.float32, (K, B))
+        if last_value is not None:
+            self._check_tensor("last_value", last_value, torch.float32, (B,))
+        if terminal_value is not None:
+            self._check_tensor("terminal_value", terminal_value, torch.float32, (K, B))
+        vl = None
+        if terminal is not None:
+            cap = int(terminal["step_env"].shape[0])
+            if (not isinstance(terminal["count"], torch.Tensor) or terminal["count"].dtype not in (torch.int32, torch.uint32)
+                    or terminal["count"].numel() != 1):
+                raise ValueError("terminal['count']: expected one 32-bit integer")
+            self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
+            self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
+            self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
+            vl = _native.SgValueList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["value"].data_ptr(), cap)
+        if out is None:
+            out = dict(advantage=torch.empty((K, B), dtype=torch.float32, device=reward.device),
+                       returns=torch.empty((K, B), dtype=torch.float32, device=reward.device))
+        else:
+            self._check_tensor("out['advantage']", out["advantage"], torch.float32, (K, B))
+            self._check_tensor("out['returns']", out["returns"], torch.float32, (K, B))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_gae_device(self._h, K, C.byref(cfg), ptr(reward), ptr(done), ptr(trunc), ptr(value), ptr(last_value),
+                                         ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(out["advantage"]),
+                                         ptr(out["returns"]), self._stream()), "sg_gae_device")
+        return out["advantage"], out["returns"]
+
+    def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
+            bootstrap_truncated=True):
+        """NumPy form of gae_torch (sg_gae): host arrays up and back.  terminal: dict count (an integer or a one-element array) /
+        step_env [n, 2] / value [n] of host arrays, e.g. from terminal_records.  Returns (advantage, returns) float32 [K, B]."""
+        if terminal_value is not None and terminal is not None:
+            raise ValueError("terminal_value and terminal: give the terminal values in one form")
+        cfg = self._gae_config(gamma, lam, bootstrap_truncated)
+        B = self.num_envs
+        if np.ndim(reward) != 2 or np.shape(reward)[0] < 1 or np.shape(reward)[1] != B:
+            raise ValueError(f"reward: expected shape (K, {B}) with K >= 1, got {np.shape(reward)}")
+        K = int(np.shape(reward)[0])
+
+        def arr(name, a, dtype, shape):
+            if a is None:
+                return None
+            a = np.asarray(a)
+            if a.dtype == np.bool_ and dtype == np.uint8:
+                a = a.view(np.uint8)
+            if a.dtype != dtype or a.shape != shape:
+                raise ValueError(f"{name}: expected {np.dtype(dtype).name} of shape {shape}, got {a.dtype} {a.shape}")
+            return np.ascontiguousarray(a)
+        reward = arr("reward", reward, np.float32, (K, B))
+        done, trunc = arr("done", done, np.uint8, (K, B)), arr("trunc", trunc, np.uint8, (K, B))
+        if done is None or trunc is None:
+            raise ValueError("done and trunc are required")
+        value, last_value = arr("value", value, np.float32, (K, B)), arr("last_value", last_value, np.float32, (B,))
+        terminal_value = arr("terminal_value", terminal_value, np.float32, (K, B))
+        vl, keep = None, None
+        if terminal is not None:
+            count = np.asarray(terminal["count"]).reshape(-1)
+            if count.size != 1 or count.dtype.kind not in "iu" or int(count[0]) < 0:
+                raise ValueError("terminal['count']: expected one non-negative integer")
+            cap = int(np.shape(terminal["step_env"])[0])
+            keep = (count.astype(np.uint32), arr("terminal['step_env']", terminal["step_env"], np.int32, (cap, 2)),
+                    arr("terminal['value']", terminal["value"], np.float32, (cap,)))
+            vl = _native.SgValueList(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, cap)
+        adv, ret = np.empty((K, B), np.float32), np.empty((K, B), np.float32)
+
+        def ptr(a):
+            return self._ptr(a) if a is not None else None
+        self._ck(self._lib.sg_gae(self._h, K, C.byref(cfg), ptr(reward), ptr(done), ptr(trunc), ptr(value), ptr(last_value),
+                                  ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(adv), ptr(ret)), "sg_gae")
+        return adv, ret
+
     def random_actions_torch(self, n_steps, seed=0, first_step=0, out=None):
         """the uniformly random policy generated on the device: [n_steps, B, 2] float32 in (-1, 1) (discrete ids: int32
         [n_steps, B] in 0..5); entry (t, i) depends only on (seed, global env index, first_step + t)."""

@@ -522,6 +522,117 @@ int sg_gae(sg_env *env, int32_t n_steps, const sg_gae_config *cfg, const float *
            const uint8_t *truncated_host, const float *value_host, const float *last_value_host,
            const float *terminal_value_dense_host, const sg_value_list *terminal_value_list, float *advantage_host, float *ret_host);
 
+/* Replay ring with uniform n-step sampling -- what an off-policy learner (SAC, TD3: the learners the reference's README names) keeps
+ * around the step: the last transitions (s, a, r, s', terminated), where s' of a finished step is the LAST observation of the episode
+ * that ended (not the first one of the next episode, which auto-reset put into obs[t]) and a truncated step still bootstraps (SB3
+ * ReplayBuffer with handle_timeout_termination, optimize_memory_usage layout).  The reference has no counterpart.
+ * The ring is device memory of the caller's in the rollout's own layout, T = steps time slots of B = num_envs envs, D = obs_dim:
+ *   obs         float32 [T, B, D]   obs[p] = the observation rows the step stored at slot p wrote (after auto-reset)
+ *   action      float32 [T, B, 2]   (discrete ids: int32 [T, B]) the action of slot p
+ *   reward      float32 [T, B]      as the stepping call wrote it
+ *   done, trunc uint8   [T, B]      as the stepping call wrote them
+ *   term_idx    uint32  [T, B]      sequence number of the terminal record of (p, i); written and read ONLY where done[p, i]
+ *   term_obs    float32 [C, D]      C = term_capacity: ring of terminal observations, record seq lives at seq mod C
+ *   slot_seq    uint32  [T]         term_head as it was before the commit that filled slot p
+ *   hdr         32 bytes            uint32 magic, T, B, D, head, filled, term_head, sample_calls (written by the kernels only)
+ * so sg_rollout_device* / sg_step_device write straight into rows of the ring (no copy on insert) and the transition stored at
+ * slot p, env i is
+ *   s  = obs[(p - 1) mod T, i]     a = action[p, i]     r = reward[p, i]
+ *   s' = term_obs[term_idx[p, i] mod C] if done[p, i], else obs[p, i]
+ *   terminated = done[p, i] and not trunc[p, i]         truncated = trunc[p, i]
+ * With filled = f and head = h the valid transitions are the v = min(f, T - 1) newest slots (h - v) mod T .. (h - 1) mod T: the
+ * oldest slot of a full ring has lost its s to the newest write, so a full ring holds T - 1 transitions per env; transition u in
+ * [0, v B) is env u mod B of slot (h - v + u / B) mod T.  Results depend on the arguments and the ring's contents only: the handle
+ * gives B, D, the action type, the device and the status word, and no env is touched.  Version 1 needs auto_reset on (the case in
+ * which the terminal observation would otherwise be lost): a handle with it off is refused.  tests/replay_model.py states all of
+ * this in NumPy, bit for bit.
+ * Every call enqueues on the caller's stream, allocates nothing, never synchronises and is hipGraph-capturable on one stream.
+ * Refused on the host by all three (SG_ERR_INVALID, nothing enqueued): a wrong struct_size, a null member, steps < 2,
+ * term_capacity outside 1 .. 2^31 - 1, steps * num_envs > 2^31 - 1, auto_reset off.  The header lives in device memory, so a ring
+ * that sg_replay_begin_device has not initialised for this T, B, D (no magic) is found on the device: such a call writes nothing
+ * and sets the status word.  Device-side refusals use status code 8: every later call on the handle fails with SG_ERR_HIP until
+ * sg_check_status has reported the condition (SG_ERR_INVALID) and cleared it. */
+typedef struct sg_replay {
+    uint32_t struct_size;    /* sizeof(sg_replay) */
+    int32_t steps;           /* T >= 2 */
+    uint32_t term_capacity;  /* C >= 1 */
+    uint32_t reserved;       /* 0 */
+    float *obs;
+    void *action;
+    float *reward;
+    uint8_t *done;
+    uint8_t *trunc;
+    uint32_t *term_idx;
+    float *term_obs;
+    uint32_t *slot_seq;
+    void *hdr;
+} sg_replay;
+/* Bytes of each member for a ring of `steps` slots on this handle, in the order of the struct (obs, action, reward, done, trunc,
+ * term_idx, term_obs, slot_seq, hdr) into member_bytes [9] (NULL to skip); returns the sum with every member rounded up to 16 bytes
+ * (one allocation cut into 16-byte aligned members), 0 for invalid arguments.  Members need their element type's alignment only. */
+size_t sg_replay_bytes(const sg_env *env, int32_t steps, uint32_t term_capacity, size_t *member_bytes);
+/* Writes the header (head = filled = term_head = sample_calls = 0) and, if obs0_dev is given, copies the [B, D] observation the
+ * first action will be taken from into obs[T - 1] (NULL: the caller wrote that row itself, e.g. sg_reset_device(obs + (T - 1) B D)). */
+int sg_replay_begin_device(sg_env *env, const sg_replay *ring, const float *obs0_dev, void *hip_stream);
+/* The caller has just had n_steps consecutive steps written into slots first_slot .. first_slot + n_steps - 1 (rollout rows, or one
+ * sg_step_device with terminal_obs) and their actions into action[...]; this makes them part of the ring.  Exactly one terminal form:
+ *   list   (a rollout's sg_terminal_list, `step` relative to first_slot): record k < min(count, capacity) gets seq = term_head + k,
+ *          its D floats go to term_obs[seq mod C] and term_idx[first_slot + t_k, i_k] = seq; then term_head += min(count, capacity).
+ *          Two launches: the records (one 16-lane group each), then one wave for the header.
+ *   dense  (n_steps == 1, float32 [B, D] as sg_step_device fills it): every env with done[first_slot, i] gets the next free sequence
+ *          number, in no particular order, and its row is copied.  Three launches (term_head noted, records, header).
+ * Then slot_seq[p] = the term_head before this commit for every committed slot, hdr.head = (first_slot + n_steps) mod T and
+ * hdr.filled = min(filled_before + n_steps, T).  The host is the authority on first_slot and filled_before: the C caller keeps the
+ * two integers (first_slot of the next commit = hdr.head of this one).  A replayed captured commit writes the same head and filled
+ * again and appends its records again: capture a commit together with the stepping call that feeds it, per slot range.
+ * Refused on the host (besides the above): first_slot < 0, n_steps < 1, first_slot + n_steps > T (a commit may not cross the end of
+ * the ring: choose T a multiple of the rollout length), filled_before outside [0, T], both or neither terminal form, the dense form
+ * with n_steps != 1, a null pointer in the list.  Checked on the device (status code 8): a list with count > capacity (records are
+ * missing); a record outside [0, n_steps) x [0, B) (ignored); and a terminal ring too small: after the commit, term_head -
+ * slot_seq[oldest valid slot] > C (unsigned, modulo 2^32; conservative by at most one commit's records), i.e. a record that a valid
+ * transition still names may have been overwritten.  That check is what lets the sampler trust term_idx. */
+int sg_replay_commit_device(sg_env *env, const sg_replay *ring, int32_t first_slot, int32_t filled_before, int32_t n_steps,
+                            const sg_terminal_list *terminal_list, const float *terminal_obs_dense_dev, void *hip_stream);
+/* A minibatch of n transitions, drawn uniformly with replacement, with n-step returns, in one launch (plus one lane that advances
+ * hdr.sample_calls on the device: a replayed captured call draws fresh indices and sees the ring grow, since head and filled are
+ * read from the header).  For draw j of the ring's call number c = hdr.sample_calls, h = hdr.head, v as above:
+ *   w      = philox4x32_10(key = seed, counter = (j lo, j hi, c, 3))        -- the engine's Philox, stream tag 3
+ *   u      = umul64hi(w0 | w1 << 32, v B)                                   -- or index_in[j] when index_in is given
+ *   q, i   = u / B, u mod B;   p_k = (h - v + q + k) mod T
+ *   k = 0:             R = (double) reward[p_0, i];  g = gamma
+ *   k = 1 .. n_step-1: stop before k if done[p_{k-1}, i] or q + k >= v (the newest edge)
+ *                      R = R + g * (double) reward[p_k, i];  g = g * gamma  -- float64, each operation rounded on its own
+ *   last = the last k included
+ *   obs = obs[(p_0 - 1) mod T, i];  action = action[p_0, i];  reward = (float) R;  discount = (float) g;  steps = last + 1
+ *   next_obs, terminated, truncated = s', terminated, truncated of (p_last, i);  index = u
+ * so the learner's target is reward + discount (1 - terminated) Q(next_obs), and with n_step = 1 the batch is the stored transition
+ * bit for bit.  index_in (int64 [n], values of u) replaces the random draw: the hook for prioritized or stratified sampling done by
+ * the caller.  A value outside [0, v B) leaves row j of every output untouched and sets status code 8; so does v = 0 with n > 0
+ * (nothing is written).  n = 0 enqueues nothing.  Refused on the host: n_step outside 1 .. 16, gamma outside [0, 1] or NaN, n < 0
+ * or > 2^31 - 1, a null batch or a null obs, action, reward, next_obs, terminated or truncated (discount, steps, index may be NULL). */
+typedef struct sg_replay_sample_config {
+    uint32_t struct_size;  /* sizeof(sg_replay_sample_config), set by sg_replay_sample_config_init */
+    uint64_t seed;         /* Philox key of the draws */
+    int32_t n_step;        /* 1 .. 16 */
+    double gamma;          /* discount, in [0, 1] */
+} sg_replay_sample_config;
+/* seed 0, n_step 1, gamma 0.99 */
+void sg_replay_sample_config_init(sg_replay_sample_config *cfg);
+typedef struct sg_replay_batch {
+    float *obs;           /* [n, D] */
+    void *action;         /* float32 [n, 2]; discrete ids: int32 [n] */
+    float *reward;        /* [n] */
+    float *next_obs;      /* [n, D] */
+    uint8_t *terminated;  /* [n] */
+    uint8_t *truncated;   /* [n] */
+    float *discount;      /* [n], may be NULL */
+    uint8_t *steps;       /* [n], may be NULL */
+    int64_t *index;       /* [n], may be NULL */
+} sg_replay_batch;
+/* cfg NULL: sg_replay_sample_config_init's values */
+int sg_replay_sample_device(sg_env *env, const sg_replay *ring, const sg_replay_sample_config *cfg, int64_t n,
+                            const int64_t *index_in_dev, const sg_replay_batch *out, void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

@@ -66,6 +66,25 @@ class SgValueList(C.Structure):
     _fields_ = [("count", C.c_void_p), ("step_env", C.c_void_p), ("value", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class SgReplay(C.Structure):
+    """sg_replay (include/spacegym.h): the members of a replay ring in device memory"""
+    _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("term_capacity", C.c_uint32), ("reserved", C.c_uint32),
+                ("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("trunc", C.c_void_p),
+                ("term_idx", C.c_void_p), ("term_obs", C.c_void_p), ("slot_seq", C.c_void_p), ("hdr", C.c_void_p)]
+
+
+class SgReplaySampleConfig(C.Structure):
+    """sg_replay_sample_config (include/spacegym.h): sg_replay_sample_config_init fills in seed 0, n_step 1, gamma 0.99"""
+    _fields_ = [("struct_size", C.c_uint32), ("seed", C.c_uint64), ("n_step", C.c_int32), ("gamma", C.c_double)]
+
+
+class SgReplayBatch(C.Structure):
+    """sg_replay_batch (include/spacegym.h): the outputs of sg_replay_sample_device"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("next_obs", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("discount", C.c_void_p), ("steps", C.c_void_p),
+                ("index", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -136,6 +155,12 @@ SYMBOLS = {
     "sg_gae_config_init": (None, [C.POINTER(SgGaeConfig)]),
     "sg_gae_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp, _vp]),
     "sg_gae": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp]),
+    "sg_replay_bytes": (C.c_size_t, [_vp, C.c_int32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    "sg_replay_begin_device": (C.c_int, [_vp, C.POINTER(SgReplay), _vp, _vp]),
+    "sg_replay_commit_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.c_int32, C.c_int32, C.c_int32, C.POINTER(SgTerminalList), _vp, _vp]),
+    "sg_replay_sample_config_init": (None, [C.POINTER(SgReplaySampleConfig)]),
+    "sg_replay_sample_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplaySampleConfig), C.c_int64, _vp,
+                                          C.POINTER(SgReplayBatch), _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

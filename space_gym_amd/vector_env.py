@@ -87,6 +87,32 @@ def check_render_size(size):
     return size
 
 
+class ReplayRing:
+    """The tensors of a replay ring (replay_torch; include/spacegym.h, sg_replay) and the host mirror of its head and fill.
+    obs [T, B, D], action [T, B, 2] (int32 [T, B]), reward, done, trunc [T, B] are the rollout's own layout: hand
+    ring.rows(K) to rollout_torch / step_torch(out=...), then replay_commit_torch(ring, K, ...).  term_idx, term_obs, slot_seq and
+    hdr are written by the commit kernels."""
+    MEMBERS = ("obs", "action", "reward", "done", "trunc", "term_idx", "term_obs", "slot_seq", "hdr")
+
+    def __init__(self, steps, num_envs, obs_dim, term_capacity, discrete, **tensors):
+        self.steps, self.num_envs, self.obs_dim, self.term_capacity, self.discrete = steps, num_envs, obs_dim, term_capacity, discrete
+        for k in self.MEMBERS:
+            setattr(self, k, tensors[k])
+        self.head = self.filled = 0
+
+    def __len__(self):
+        """valid transitions: min(filled, T - 1) slots of the whole batch"""
+        return min(self.filled, self.steps - 1) * self.num_envs
+
+    def rows(self, n_steps):
+        """views of the next n_steps slots (obs, action, reward, done, trunc), to be written by the stepping call"""
+        K = int(n_steps)
+        if K < 1 or self.head + K > self.steps:
+            raise ValueError(f"rows: slots {self.head} .. {self.head + K - 1} cross the end of a ring of {self.steps}")
+        p = self.head
+        return {k: getattr(self, k)[p:p + K] for k in ("obs", "action", "reward", "done", "trunc")}
+
+
 class SpaceGymVectorEnv:
     metadata = {"render.modes": ["rgb_array"]}
 
@@ -462,6 +488,7 @@ class SpaceGymVectorEnv:
 
     def set_auto_reset(self, on):
         self._ck(self._lib.sg_set_auto_reset(self._h, int(bool(on))), "sg_set_auto_reset")
+        self._cfg.auto_reset = int(bool(on))
 
     # ------------------------------------------------------------------ NumPy path
     @staticmethod
@@ -1062,6 +1089,142 @@ class SpaceGymVectorEnv:
         self._ck(self._lib.sg_gae(self._h, K, C.byref(cfg), ptr(reward), ptr(done), ptr(trunc), ptr(value), ptr(last_value),
                                   ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(adv), ptr(ret)), "sg_gae")
         return adv, ret
+
+    # ------------------------------------------------------------------ replay ring with uniform n-step sampling
+    def replay_torch(self, steps, term_capacity=None):
+        """A replay ring of `steps` time slots of the whole batch in device memory (ReplayRing): its rows are the tensors
+        rollout_torch / step_torch(out=...) write into, so inserting copies nothing.  term_capacity: terminal observations kept
+        (default max(2 B, T B // 16): a whole batch may truncate in one step, and the random policy finishes about 2 % of the
+        env-steps).  Call replay_begin_torch before the first step."""
+        import torch
+        T, B, D = int(steps), self.num_envs, self.obs_dim
+        if T < 2:
+            raise ValueError(f"steps: at least 2 expected, got {T}")
+        if T * B > 2 ** 31 - 1:
+            raise ValueError(f"steps * num_envs = {T * B}: at most 2^31 - 1 (transitions are addressed by 32 bits)")
+        cap = max(2 * B, T * B // 16) if term_capacity is None else int(term_capacity)
+        if not 1 <= cap <= 2 ** 31 - 1:
+            raise ValueError(f"term_capacity: 1 .. 2^31 - 1 expected, got {cap}")
+        self._replay_need_auto_reset("replay_torch")
+        dev = torch.device("cuda", self.device)
+        e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
+        return ReplayRing(
+            steps=T, num_envs=B, obs_dim=D, term_capacity=cap, discrete=self.discrete, obs=e((T, B, D), torch.float32),
+            action=e((T, B), torch.int32) if self.discrete else e((T, B, 2), torch.float32), reward=e((T, B), torch.float32),
+            done=e((T, B), torch.uint8), trunc=e((T, B), torch.uint8), term_idx=e((T, B), torch.int32),
+            term_obs=e((cap, D), torch.float32), slot_seq=e((T,), torch.int32), hdr=torch.zeros(8, dtype=torch.int32, device=dev))
+
+    def _replay_need_auto_reset(self, what):
+        if not self._cfg.auto_reset:
+            raise ValueError(f"{what}: the replay ring needs auto_reset on (with it off obs[t] of a finished step is the terminal "
+                             "observation itself)")
+
+    def _replay_arg(self, ring):
+        """SgReplay over the tensors of a ReplayRing, checked"""
+        import torch
+        if not isinstance(ring, ReplayRing):
+            raise ValueError("ring: expected the object replay_torch returned")
+        T, B, D, cap = ring.steps, self.num_envs, self.obs_dim, ring.term_capacity
+        if ring.num_envs != B or ring.obs_dim != D or ring.discrete != self.discrete:
+            raise ValueError("ring: made for another batch size, observation width or action type")
+        self._check_tensor("ring.obs", ring.obs, torch.float32, (T, B, D))
+        self._check_tensor("ring.action", ring.action, torch.int32 if self.discrete else torch.float32, (T, B) if self.discrete else (T, B, 2))
+        self._check_tensor("ring.reward", ring.reward, torch.float32, (T, B))
+        self._check_tensor("ring.done", ring.done, torch.uint8, (T, B))
+        self._check_tensor("ring.trunc", ring.trunc, torch.uint8, (T, B))
+        self._check_tensor("ring.term_idx", ring.term_idx, torch.int32, (T, B))
+        self._check_tensor("ring.term_obs", ring.term_obs, torch.float32, (cap, D))
+        self._check_tensor("ring.slot_seq", ring.slot_seq, torch.int32, (T,))
+        self._check_tensor("ring.hdr", ring.hdr, torch.int32, (8,))
+        self._replay_need_auto_reset("ring")
+        return _native.SgReplay(C.sizeof(_native.SgReplay), T, cap, 0, *(getattr(ring, k).data_ptr() for k in ReplayRing.MEMBERS))
+
+    def replay_begin_torch(self, ring, obs0=None):
+        """Empties the ring (sg_replay_begin_device).  obs0: float32 [B, D], the observation the first action will be taken from,
+        copied into ring.obs[T - 1]; None: the caller wrote that row itself, e.g. reset_torch(out=ring.obs[ring.steps - 1])."""
+        import torch
+        r = self._replay_arg(ring)
+        if obs0 is not None:
+            self._check_tensor("obs0", obs0, torch.float32, (self.num_envs, self.obs_dim))
+        self._ck(self._lib.sg_replay_begin_device(self._h, C.byref(r), C.c_void_p(obs0.data_ptr()) if obs0 is not None else None,
+                                                  self._stream()), "sg_replay_begin_device")
+        ring.head = ring.filled = 0
+        return ring
+
+    def replay_commit_torch(self, ring, n_steps, terminal=None, terminal_obs=None):
+        """Makes the n_steps slots at the ring's head, which the caller has just had written (ring.rows(n_steps): rollout_torch
+        rows with their actions, or one step_torch(out=..., terminal_obs=...)), part of the ring (sg_replay_commit_device).
+        Exactly one of terminal (the rollout's terminal list, terminal_list_torch) and terminal_obs (float32 [B, D] of one step).
+        A commit may not cross the end of the ring: choose `steps` a multiple of the rollout length."""
+        import torch
+        r = self._replay_arg(ring)
+        K, T, D = int(n_steps), ring.steps, self.obs_dim
+        if K < 1:
+            raise ValueError(f"n_steps: at least 1 expected, got {K}")
+        if ring.head + K > T:
+            raise ValueError(f"n_steps: slots {ring.head} .. {ring.head + K - 1} cross the end of a ring of {T} (choose steps a "
+                             "multiple of the rollout length)")
+        if (terminal is None) == (terminal_obs is None):
+            raise ValueError("terminal and terminal_obs: exactly one terminal form expected")
+        tl = None
+        if terminal is not None:
+            cap = int(terminal["step_env"].shape[0])
+            if (not isinstance(terminal["count"], torch.Tensor) or terminal["count"].dtype not in (torch.int32, torch.uint32)
+                    or terminal["count"].numel() != 1):
+                raise ValueError("terminal['count']: expected one 32-bit integer")
+            self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
+            self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
+            self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, D))
+            tl = _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap)
+        else:
+            if K != 1:
+                raise ValueError(f"terminal_obs: dense terminal observations describe one step, n_steps = {K}")
+            self._check_tensor("terminal_obs", terminal_obs, torch.float32, (self.num_envs, D))
+        self._ck(self._lib.sg_replay_commit_device(self._h, C.byref(r), ring.head, ring.filled, K, C.byref(tl) if tl is not None else None,
+                                                   C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None,
+                                                   self._stream()), "sg_replay_commit_device")
+        ring.head, ring.filled = (ring.head + K) % T, min(ring.filled + K, T)
+        return ring
+
+    def replay_sample_torch(self, ring, n, seed=0, n_step=1, gamma=0.99, index=None, out=None):
+        """A minibatch of n transitions drawn uniformly with replacement, with n_step-step returns (sg_replay_sample_device: one
+        launch; torch's current stream, no host synchronisation, graph-capturable: a replayed call draws fresh indices).  Returns
+        a dict obs [n, D], action [n, 2] (int32 [n]), reward, next_obs [n, D], terminated, truncated (uint8), discount, steps
+        (uint8), index (int64): the target is reward + discount * (1 - terminated) * Q(next_obs).  index: int64 [n] of transition
+        numbers in [0, len(ring)) to gather instead of drawing.  out: such a dict to write into (discount, steps, index optional).
+        tests/replay_model.py states the arithmetic."""
+        import torch
+        r = self._replay_arg(ring)
+        n, n_step, gamma, seed = int(n), int(n_step), float(gamma), int(seed)
+        B, D = self.num_envs, self.obs_dim
+        if not 0 <= n <= 2 ** 31 - 1:
+            raise ValueError(f"n: 0 .. 2^31 - 1 expected, got {n}")
+        if not 1 <= n_step <= 16:
+            raise ValueError(f"n_step: 1 .. 16 expected, got {n_step}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed: an unsigned 64-bit integer expected, got {seed}")
+        if n > 0 and len(ring) == 0:
+            raise ValueError("ring: no valid transition yet (commit at least one step)")
+        if index is not None:
+            self._check_tensor("index", index, torch.int64, (n,))
+        spec = dict(obs=(torch.float32, (n, D)), action=(torch.int32, (n,)) if self.discrete else (torch.float32, (n, 2)),
+                    reward=(torch.float32, (n,)), next_obs=(torch.float32, (n, D)), terminated=(torch.uint8, (n,)),
+                    truncated=(torch.uint8, (n,)), discount=(torch.float32, (n,)), steps=(torch.uint8, (n,)), index=(torch.int64, (n,)))
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (dtype, shape) in spec.items()}
+        else:
+            for k, (dtype, shape) in spec.items():
+                if k in out or k not in ("discount", "steps", "index"):
+                    self._check_tensor(f"out['{k}']", out[k], dtype, shape)
+        cfg = _native.SgReplaySampleConfig(C.sizeof(_native.SgReplaySampleConfig), seed, n_step, gamma)
+        batch = _native.SgReplayBatch(*(out[k].data_ptr() if k in out else None for k in spec))
+        self._ck(self._lib.sg_replay_sample_device(self._h, C.byref(r), C.byref(cfg), n,
+                                                   C.c_void_p(index.data_ptr()) if index is not None else None, C.byref(batch),
+                                                   self._stream()), "sg_replay_sample_device")
+        return out
 
     def random_actions_torch(self, n_steps, seed=0, first_step=0, out=None):
         """the uniformly random policy generated on the device: [n_steps, B, 2] float32 in (-1, 1) (discrete ids: int32

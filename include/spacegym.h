@@ -633,6 +633,86 @@ typedef struct sg_replay_batch {
 int sg_replay_sample_device(sg_env *env, const sg_replay *ring, const sg_replay_sample_config *cfg, int64_t n,
                             const int64_t *index_in_dev, const sg_replay_batch *out, void *hip_stream);
 
+/* Prioritized sampling from the replay ring (Schaul et al. 2016, proportional variant) with an exact integer sum tree.  A
+ * caller-owned device object next to the ring holds one priority per cell c = p B + i (slot p, env i: by slot, so nothing moves when
+ * the ring wraps) as an UNSIGNED FIXED-POINT INTEGER q with frac_bits fractional bits; every sum over them is a 64-bit integer.
+ * Integer addition is associative: the contents do not depend on reduction order or on the arrival order of atomics, never drift,
+ * and the draw is defined without reference to any tree:
+ *     the cell chosen for a number r in [0, total) is the smallest cell c with q[0] + ... + q[c] > r.
+ * `node` holds partial sums that serve that definition: opaque memory whose layout is the library's business.  q = 0 marks a cell
+ * that holds no valid transition (the hole slot whose s the newest write destroyed, a slot never filled): it is never drawn.
+ * Exponents (|delta|^alpha, (N P)^-beta) are the only inexact arithmetic and are kept out of the integer state: the priority
+ * handed to sg_priority_update_device is already raised to alpha.  tests/priority_model.py states all of this in NumPy.
+ * Every call enqueues on the caller's stream, allocates nothing, never synchronises and is hipGraph-capturable on one stream (no
+ * parallel branches).  Refused on the host by every call (SG_ERR_INVALID, nothing enqueued): a wrong struct_size, a null member,
+ * leaf or node not 16-byte aligned, steps < 2, steps * num_envs > 2^31 - 1, frac_bits outside 0 .. 31, auto_reset off.  An object
+ * that sg_priority_begin_device has not initialised for this T, B, frac_bits (no magic) is found on the device.  Device-side
+ * refusals use status code 9: every later call on the handle fails with SG_ERR_HIP until sg_check_status has reported the
+ * condition (SG_ERR_INVALID) and cleared it. */
+typedef struct sg_priority {
+    uint32_t struct_size;  /* sizeof(sg_priority) */
+    int32_t steps;         /* T of the ring */
+    int32_t frac_bits;     /* 0 .. 31: priority 1.0 is q = 1 << frac_bits */
+    uint32_t reserved;     /* 0 */
+    uint32_t *leaf;        /* [T, B]  q of cell c = p * B + i, ring layout */
+    uint64_t *node;        /* opaque partial sums, size from sg_priority_bytes */
+    void *hdr;             /* 64 bytes: uint32 magic, T, B, frac_bits, head, filled, max_q, sample_calls; uint64 total; reserved */
+} sg_priority;
+/* Bytes of leaf, node and hdr for a ring of `steps` slots on this handle into member_bytes [3] (NULL to skip); returns the sum with
+ * every member rounded up to 16 bytes, 0 for invalid arguments. */
+size_t sg_priority_bytes(const sg_env *env, int32_t steps, size_t *member_bytes);
+/* All leaves and nodes 0, total = 0, head = filled = sample_calls = 0, max_q = 1 << frac_bits (priority 1.0). */
+int sg_priority_begin_device(sg_env *env, const sg_priority *prio, void *hip_stream);
+/* Called after sg_replay_commit_device, with the same three integers: every cell of slots first_slot .. first_slot + n_steps - 1
+ * gets max_q (a new transition is seen at least once), every cell of slot (first_slot + n_steps) mod T gets 0 (the hole: the slot
+ * whose s the newest write destroyed; on a ring that is not yet full it is 0 already), and total, the nodes, head and filled follow.
+ * Host refusals are those of sg_replay_commit_device: first_slot < 0, n_steps < 1, first_slot + n_steps > T, filled_before outside
+ * [0, T]. */
+int sg_priority_commit_device(sg_env *env, const sg_priority *prio, int32_t first_slot, int32_t filled_before, int32_t n_steps,
+                              void *hip_stream);
+/* New priorities for n cells: cell_dev int64 [n] (the `cell` a draw returned: unlike `index` it does not shift with the next
+ * commit), priority_dev float32 [n], already raised to alpha.  q = clamp(rint((double) p * 2^frac_bits), 1, 2^32 - 1), exact in
+ * float64 (p = 0 gives q = 1).  Duplicates of a cell within one call: the LARGEST q wins, so the result does not depend on order.
+ * A cell outside the current valid window (the hole, or a never-filled slot) is skipped silently: that is the ordinary race between
+ * a learner and the collector overwriting the ring, and it never makes an invalid cell samplable.  Status code 9 (row skipped) for a
+ * cell outside [0, T B) and for a p that is NaN, negative or infinite.  max_q = max(max_q, every applied q).  n = 0 enqueues nothing.
+ * Refused on the host: n outside 0 .. 2^31 - 1, a null cell_dev or priority_dev with n > 0. */
+int sg_priority_update_device(sg_env *env, const sg_priority *prio, int64_t n, const int64_t *cell_dev, const float *priority_dev,
+                              void *hip_stream);
+/* n draws in proportion to q.  For draw j of the object's call number c = hdr.sample_calls, with v = min(filled, T - 1):
+ *   w = philox4x32_10(key = seed, counter = (j lo, j hi, c, 4))                  -- the engine's Philox, stream tag 4
+ *   x = w0 | w1 << 32
+ *   stratified:   len_j = total / n + (j < total mod n);  lo_j = j (total / n) + min(j, total mod n);  r = lo_j + umul64hi(x, len_j)
+ *                 (the strata tile [0, total) exactly; 64-bit arithmetic only)
+ *   independent:  r = umul64hi(x, total)
+ *   cell   = the smallest c with q[0] + ... + q[c] > r;   p, i = cell / B, cell mod B;   leaf = q[cell]
+ *   index  = ((p - (head - v)) mod T) B + i               -- the transition number sg_replay_sample_device takes as index_in
+ *   weight = (float) pow(((double) (v B) * (double) q) / (double) total, -beta)  -- each operation rounded on its own; unnormalised;
+ *                                                                                   beta = 0 gives exactly 1
+ * sample_calls advances on the device, so a replayed captured call draws afresh.  The gather of the drawn transitions is
+ * sg_replay_sample_device with index_in = index, enqueued by the caller.  Status code 9, nothing written: no matching header;
+ * total = 0 with n > 0; stratified with total < n; hdr.head / hdr.filled of the priorities different from the ring's (a commit was
+ * forgotten); and, for its own row, a drawn cell outside the valid window (impossible if the structure is right: a check, not a
+ * path).  n = 0 enqueues nothing.  Refused on the host: a null ring, cfg struct_size, steps different from the ring's, beta negative
+ * or NaN, n outside 0 .. 2^31 - 1, a null out, index or weight (cell and leaf may be NULL). */
+typedef struct sg_priority_sample_config {
+    uint32_t struct_size;  /* sizeof(sg_priority_sample_config), set by sg_priority_sample_config_init */
+    uint64_t seed;         /* Philox key of the draws */
+    double beta;           /* importance exponent, >= 0 */
+    int32_t stratified;    /* 1: one draw per stratum of [0, total); 0: independent draws */
+} sg_priority_sample_config;
+/* seed 0, beta 0.4, stratified 1 */
+void sg_priority_sample_config_init(sg_priority_sample_config *cfg);
+typedef struct sg_priority_draw {
+    int64_t *index;   /* [n] */
+    int64_t *cell;    /* [n], may be NULL */
+    float *weight;    /* [n] */
+    uint32_t *leaf;   /* [n], may be NULL */
+} sg_priority_draw;
+/* cfg NULL: sg_priority_sample_config_init's values */
+int sg_priority_sample_device(sg_env *env, const sg_replay *ring, const sg_priority *prio, const sg_priority_sample_config *cfg,
+                              int64_t n, const sg_priority_draw *out, void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

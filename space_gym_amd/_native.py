@@ -85,6 +85,22 @@ class SgReplayBatch(C.Structure):
                 ("index", C.c_void_p)]
 
 
+class SgPriority(C.Structure):
+    """sg_priority (include/spacegym.h): the members of the priorities of a replay ring in device memory"""
+    _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("frac_bits", C.c_int32), ("reserved", C.c_uint32),
+                ("leaf", C.c_void_p), ("node", C.c_void_p), ("hdr", C.c_void_p)]
+
+
+class SgPrioritySampleConfig(C.Structure):
+    """sg_priority_sample_config (include/spacegym.h): sg_priority_sample_config_init fills in seed 0, beta 0.4, stratified 1"""
+    _fields_ = [("struct_size", C.c_uint32), ("seed", C.c_uint64), ("beta", C.c_double), ("stratified", C.c_int32)]
+
+
+class SgPriorityDraw(C.Structure):
+    """sg_priority_draw (include/spacegym.h): the outputs of sg_priority_sample_device"""
+    _fields_ = [("index", C.c_void_p), ("cell", C.c_void_p), ("weight", C.c_void_p), ("leaf", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -161,6 +177,13 @@ SYMBOLS = {
     "sg_replay_sample_config_init": (None, [C.POINTER(SgReplaySampleConfig)]),
     "sg_replay_sample_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplaySampleConfig), C.c_int64, _vp,
                                           C.POINTER(SgReplayBatch), _vp]),
+    "sg_priority_bytes": (C.c_size_t, [_vp, C.c_int32, C.POINTER(C.c_size_t)]),
+    "sg_priority_begin_device": (C.c_int, [_vp, C.POINTER(SgPriority), _vp]),
+    "sg_priority_commit_device": (C.c_int, [_vp, C.POINTER(SgPriority), C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "sg_priority_update_device": (C.c_int, [_vp, C.POINTER(SgPriority), C.c_int64, _vp, _vp, _vp]),
+    "sg_priority_sample_config_init": (None, [C.POINTER(SgPrioritySampleConfig)]),
+    "sg_priority_sample_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgPriority), C.POINTER(SgPrioritySampleConfig), C.c_int64,
+                                            C.POINTER(SgPriorityDraw), _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -113,6 +113,17 @@ class ReplayRing:
         return {k: getattr(self, k)[p:p + K] for k in ("obs", "action", "reward", "done", "trunc")}
 
 
+class ReplayPriority:
+    """The priorities of a replay ring (replay_priority_torch; include/spacegym.h, sg_priority): leaf int32 [T, B] holds the bits of
+    the uint32 fixed-point priority q of every cell (0: not samplable), node int64 the library's partial sums (opaque), hdr int32
+    [16] the 64-byte header (magic, T, B, frac_bits, head, filled, max_q, sample_calls, then the uint64 total)."""
+    MEMBERS = ("leaf", "node", "hdr")
+
+    def __init__(self, steps, num_envs, frac_bits, leaf, node, hdr):
+        self.steps, self.num_envs, self.frac_bits = steps, num_envs, frac_bits
+        self.leaf, self.node, self.hdr = leaf, node, hdr
+
+
 class SpaceGymVectorEnv:
     metadata = {"render.modes": ["rgb_array"]}
 
@@ -1151,13 +1162,15 @@ class SpaceGymVectorEnv:
         ring.head = ring.filled = 0
         return ring
 
-    def replay_commit_torch(self, ring, n_steps, terminal=None, terminal_obs=None):
+    def replay_commit_torch(self, ring, n_steps, terminal=None, terminal_obs=None, priority=None):
         """Makes the n_steps slots at the ring's head, which the caller has just had written (ring.rows(n_steps): rollout_torch
         rows with their actions, or one step_torch(out=..., terminal_obs=...)), part of the ring (sg_replay_commit_device).
         Exactly one of terminal (the rollout's terminal list, terminal_list_torch) and terminal_obs (float32 [B, D] of one step).
-        A commit may not cross the end of the ring: choose `steps` a multiple of the rollout length."""
+        A commit may not cross the end of the ring: choose `steps` a multiple of the rollout length.
+        priority: the ring's ReplayPriority: its commit (sg_priority_commit_device) follows with the same integers."""
         import torch
         r = self._replay_arg(ring)
+        pr = self._priority_arg(priority, ring) if priority is not None else None
         K, T, D = int(n_steps), ring.steps, self.obs_dim
         if K < 1:
             raise ValueError(f"n_steps: at least 1 expected, got {K}")
@@ -1183,7 +1196,11 @@ class SpaceGymVectorEnv:
         self._ck(self._lib.sg_replay_commit_device(self._h, C.byref(r), ring.head, ring.filled, K, C.byref(tl) if tl is not None else None,
                                                    C.c_void_p(terminal_obs.data_ptr()) if terminal_obs is not None else None,
                                                    self._stream()), "sg_replay_commit_device")
-        ring.head, ring.filled = (ring.head + K) % T, min(ring.filled + K, T)
+        first, filled = ring.head, ring.filled
+        ring.head, ring.filled = (first + K) % T, min(filled + K, T)  # (the device ring has moved, whatever follows)
+        if pr is not None:
+            self._ck(self._lib.sg_priority_commit_device(self._h, C.byref(pr), first, filled, K, self._stream()),
+                     "sg_priority_commit_device")
         return ring
 
     def replay_sample_torch(self, ring, n, seed=0, n_step=1, gamma=0.99, index=None, out=None):
@@ -1225,6 +1242,142 @@ class SpaceGymVectorEnv:
                                                    C.c_void_p(index.data_ptr()) if index is not None else None, C.byref(batch),
                                                    self._stream()), "sg_replay_sample_device")
         return out
+
+    # ------------------------------------------------------------------ prioritized sampling with an exact integer sum tree
+    def replay_priority_torch(self, ring, frac_bits=16):
+        """The priorities of `ring` in device memory (ReplayPriority): one unsigned fixed-point integer with frac_bits fractional
+        bits per cell, and the partial sums over them (64-bit integers: exact, order-independent, never drifting).  Call
+        replay_priority_begin_torch before the first commit."""
+        import torch
+        self._replay_arg(ring)
+        frac_bits = int(frac_bits)
+        if not 0 <= frac_bits <= 31:
+            raise ValueError(f"frac_bits: 0 .. 31 expected, got {frac_bits}")
+        T, B = ring.steps, self.num_envs
+        m = (C.c_size_t * 3)()
+        if not self._lib.sg_priority_bytes(self._h, T, m):
+            raise ValueError(f"replay_priority_torch: sg_priority_bytes refused steps = {T}")
+        dev = torch.device("cuda", self.device)
+        return ReplayPriority(T, B, frac_bits, leaf=torch.empty((T, B), dtype=torch.int32, device=dev),
+                              node=torch.empty(m[1] // 8, dtype=torch.int64, device=dev), hdr=torch.zeros(16, dtype=torch.int32, device=dev))
+
+    def _priority_arg(self, prio, ring=None):
+        """SgPriority over the tensors of a ReplayPriority, checked"""
+        import torch
+        if not isinstance(prio, ReplayPriority):
+            raise ValueError("priority: expected the object replay_priority_torch returned")
+        T, B = prio.steps, self.num_envs
+        if prio.num_envs != B:
+            raise ValueError("priority: made for another batch size")
+        if ring is not None and ring.steps != T:
+            raise ValueError(f"priority: made for a ring of {T} slots, this ring has {ring.steps}")
+        if not 0 <= prio.frac_bits <= 31:
+            raise ValueError(f"priority: frac_bits 0 .. 31 expected, got {prio.frac_bits}")
+        self._check_tensor("priority.leaf", prio.leaf, torch.int32, (T, B))
+        self._check_tensor("priority.node", prio.node, torch.int64, tuple(prio.node.shape))
+        if prio.node.dim() != 1:
+            raise ValueError("priority.node: a one-dimensional tensor expected")
+        self._check_tensor("priority.hdr", prio.hdr, torch.int32, (16,))
+        self._replay_need_auto_reset("priority")
+        return _native.SgPriority(C.sizeof(_native.SgPriority), T, prio.frac_bits, 0, prio.leaf.data_ptr(), prio.node.data_ptr(),
+                                  prio.hdr.data_ptr())
+
+    def replay_priority_begin_torch(self, prio):
+        """Empties the priorities (sg_priority_begin_device): every cell 0, max priority 1.0."""
+        p = self._priority_arg(prio)
+        self._ck(self._lib.sg_priority_begin_device(self._h, C.byref(p), self._stream()), "sg_priority_begin_device")
+        return prio
+
+    def replay_priority_commit_torch(self, prio, first_slot, filled_before, n_steps):
+        """sg_priority_commit_device on its own, with the three integers of the ring's commit (replay_commit_torch(priority=...)
+        does both): the committed slots get the largest priority seen so far, the hole slot 0."""
+        p = self._priority_arg(prio)
+        first, filled, K, T = int(first_slot), int(filled_before), int(n_steps), prio.steps
+        if K < 1 or first < 0 or first + K > T:
+            raise ValueError(f"n_steps: slots {first} .. {first + K - 1} cross the end of a ring of {T}")
+        if not 0 <= filled <= T:
+            raise ValueError(f"filled_before: 0 .. {T} expected, got {filled}")
+        self._ck(self._lib.sg_priority_commit_device(self._h, C.byref(p), first, filled, K, self._stream()), "sg_priority_commit_device")
+        return prio
+
+    def replay_update_priorities_torch(self, prio, cell, td_error=None, alpha=0.6, epsilon=1e-6, priority=None):
+        """New priorities for the cells a prioritized batch named (sg_priority_update_device): (|td_error| + epsilon) ** alpha,
+        computed in torch, or `priority` (float32 [n], already raised to alpha) passed straight through.  Duplicates: the largest
+        wins; cells the collector has overwritten meanwhile are skipped."""
+        import torch
+        p = self._priority_arg(prio)
+        if (td_error is None) == (priority is None):
+            raise ValueError("td_error and priority: exactly one expected")
+        if not isinstance(cell, torch.Tensor) or cell.dim() != 1:
+            raise ValueError("cell: a one-dimensional int64 tensor expected")
+        n = int(cell.shape[0])
+        self._check_tensor("cell", cell, torch.int64, (n,))
+        if priority is None:
+            alpha, epsilon = float(alpha), float(epsilon)
+            if not alpha >= 0.0 or not epsilon >= 0.0:
+                raise ValueError(f"alpha and epsilon must be >= 0, got {alpha}, {epsilon}")
+            self._check_tensor("td_error", td_error, torch.float32, (n,))
+            priority = (td_error.abs() + epsilon) ** alpha
+        else:
+            self._check_tensor("priority", priority, torch.float32, (n,))
+        self._ck(self._lib.sg_priority_update_device(self._h, C.byref(p), n, C.c_void_p(cell.data_ptr()), C.c_void_p(priority.data_ptr()),
+                                                     self._stream()), "sg_priority_update_device")
+        return prio
+
+    def replay_priority_draw_torch(self, ring, prio, n, seed=0, beta=0.4, stratified=True, out=None):
+        """n draws in proportion to the priorities (sg_priority_sample_device: one launch plus the call counter; no host
+        synchronisation, graph-capturable: a replayed call draws afresh).  Returns a dict index (int64 [n], transition numbers for
+        replay_sample_torch(index=...)), cell (int64 [n], the handle for replay_update_priorities_torch), weight (float32 [n],
+        (N P)^-beta, unnormalised) and leaf (int32 [n], the bits of the drawn uint32 priorities).  out: such a dict to write into
+        (cell and leaf optional).  tests/priority_model.py states the arithmetic."""
+        import torch
+        r = self._replay_arg(ring)
+        p = self._priority_arg(prio, ring)
+        n, seed, beta = int(n), int(seed), float(beta)
+        if not 0 <= n <= 2 ** 31 - 1:
+            raise ValueError(f"n: 0 .. 2^31 - 1 expected, got {n}")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed: an unsigned 64-bit integer expected, got {seed}")
+        if not 0.0 <= beta < float("inf"):
+            raise ValueError(f"beta must be finite and >= 0, got {beta}")
+        if n > 0 and len(ring) == 0:
+            raise ValueError("ring: no valid transition yet (commit at least one step)")
+        spec = dict(index=torch.int64, cell=torch.int64, weight=torch.float32, leaf=torch.int32)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.empty((n,), dtype=dtype, device=dev) for k, dtype in spec.items()}
+        else:
+            for k, dtype in spec.items():
+                if k in out or k not in ("cell", "leaf"):
+                    self._check_tensor(f"out['{k}']", out[k], dtype, (n,))
+        cfg = _native.SgPrioritySampleConfig(C.sizeof(_native.SgPrioritySampleConfig), seed, beta, int(bool(stratified)))
+        draw = _native.SgPriorityDraw(*(out[k].data_ptr() if k in out else None for k in spec))
+        self._ck(self._lib.sg_priority_sample_device(self._h, C.byref(r), C.byref(p), C.byref(cfg), n, C.byref(draw), self._stream()),
+                 "sg_priority_sample_device")
+        return out
+
+    def replay_sample_prioritized_torch(self, ring, prio, n, seed=0, beta=0.4, stratified=True, n_step=1, gamma=0.99, normalize=True,
+                                        out=None):
+        """A minibatch of n transitions drawn in proportion to their priorities, with n_step-step returns: the draw
+        (replay_priority_draw_torch), then the gather through replay_sample_torch(index=...).  Returns the uniform sampler's dict
+        plus cell (int64) and weight (float32).  normalize: weight is divided by the batch maximum, in place, without a
+        synchronisation (Dopamine's convention); False leaves (N P)^-beta.  out: such a dict to write into (discount, steps
+        optional)."""
+        draw_out = gather_out = None
+        if out is not None:
+            missing = [k for k in ("index", "cell", "weight") if k not in out]
+            if missing:
+                raise ValueError(f"out: {', '.join(missing)} missing (index, cell and weight are required; leaf, discount, steps optional)")
+            draw_out = {k: out[k] for k in ("index", "cell", "weight", "leaf") if k in out}
+            gather_out = {k: v for k, v in out.items() if k not in ("cell", "weight", "leaf")}
+        d = self.replay_priority_draw_torch(ring, prio, n, seed=seed, beta=beta, stratified=stratified, out=draw_out)
+        batch = self.replay_sample_torch(ring, n, seed=seed, n_step=n_step, gamma=gamma, index=d["index"], out=gather_out)
+        if int(n) > 0 and normalize:
+            d["weight"].div_(d["weight"].max())
+        if out is not None:
+            return out
+        batch["index"], batch["cell"], batch["weight"] = d["index"], d["cell"], d["weight"]
+        return batch
 
     def random_actions_torch(self, n_steps, seed=0, first_step=0, out=None):
         """the uniformly random policy generated on the device: [n_steps, B, 2] float32 in (-1, 1) (discrete ids: int32

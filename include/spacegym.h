@@ -713,6 +713,73 @@ typedef struct sg_priority_draw {
 int sg_priority_sample_device(sg_env *env, const sg_replay *ring, const sg_priority *prio, const sg_priority_sample_config *cfg,
                               int64_t n, const sg_priority_draw *out, void *hip_stream);
 
+/* Closed-loop rollouts: a small MLP actor-critic evaluated, sampled and scored on the device, so that a PPO / A2C learner's
+ * collection loop is the engine's own work: one launch per env-step beside the step kernel instead of an eager forward, a
+ * torch.distributions sample and a log_prob.  The reference has no counterpart.  The parametrisation is SB3's / CleanRL's:
+ *   actor    obs_dim -> hidden (x n_hidden) -> head     head = 2 (continuous ids: the mean) or 6 (discrete ids: the logits)
+ *   critic   obs_dim -> hidden (x n_hidden) -> 1        optional, a net of its own (nothing is shared with the actor)
+ *   log_std  [2], state-independent                     continuous ids only
+ * Every hidden layer is followed by the activation; the heads are linear.  All parameters are float32 DEVICE pointers in
+ * torch.nn.Linear layout -- weight [out, in] row-major, bias [out] -- owned by the caller and read in place at every call: a
+ * learner's parameters are used where they are, no copy, no transpose, and an optimizer step is seen by the next call.
+ * Arithmetic: float32 throughout.  Output neuron j of a layer is fmaf(W[j][k], h[k], .) over k = 0, 1, ... starting from b[j], one
+ * env per lane: no atomics, no cross-lane reduction, so env i's results depend on its own observation row, the parameters and
+ * (seed, step, env_index_base + i) only -- not on the batch size, the env's position in the batch or how a job is sharded.
+ * Randomness: o = philox4x32_10(key = seed, counter = (env_index_base + i, step lo, step hi, 5)) -- the engine's Philox, stream tag 5,
+ * one block per env-step; u23(w) = ((w >> 9) + 0.5) / 2^23.
+ *   continuous  eps0 = sqrt(-2 ln u23(o0)) cos(2 pi u23(o1)), eps1 the same with sin (o2, o3 would serve a second pair)
+ *               action = mean + exp(log_std) * eps          stored UNCLAMPED: the step clamps on the device itself, and
+ *               logp   = sum(-eps^2 / 2 - log_std - ln(2 pi) / 2)   is that of the unclamped Gaussian, as SB3 computes it
+ *   discrete    p_j = exp(logit_j - max logit), total = p_0 + ... + p_5; action = the first j with p_0 + ... + p_j >= u23(o0) * total
+ *               logp = log_softmax(logits)[action]
+ *   deterministic != 0: action = the mean / the first argmax, logp = that action's log-prob; nothing is drawn.
+ * tests/policy_model.py states this in NumPy float64; DESIGN section 17 has the kernel and the tolerances. */
+#define SG_POLICY_TANH 0
+#define SG_POLICY_RELU 1
+typedef struct sg_policy_mlp {
+    const float *weight[4];  /* layer l < n_hidden: [hidden, in_l] (in_0 = obs_dim, then hidden); layer n_hidden: the head [head, hidden] */
+    const float *bias[4];    /* [hidden] ... , [head]; entries past n_hidden are ignored */
+} sg_policy_mlp;
+typedef struct sg_policy {
+    uint32_t struct_size;  /* sizeof(sg_policy) */
+    int32_t n_hidden;      /* hidden layers of each net, 1 .. 3 */
+    int32_t hidden;        /* their width, 1 .. 128 */
+    int32_t activation;    /* SG_POLICY_TANH / SG_POLICY_RELU */
+    int32_t head;          /* outputs of the actor: 2 for the continuous ids, 6 for the discrete ones (anything else is refused) */
+    int32_t reserved;      /* 0 */
+    sg_policy_mlp actor;
+    sg_policy_mlp critic;  /* weight[0] == NULL: no critic (every other pointer of it is then ignored) */
+    const float *log_std;  /* [2], continuous ids; must be NULL for the discrete ids */
+} sg_policy;
+/* (action, logp, value) of the observation rows obs_dev float32 [num_envs, obs_dim] in ONE launch on the stream: action_out float32
+ * [num_envs, 2] (discrete ids: int32 [num_envs]), logp_out float32 [num_envs] (may be NULL), value_out float32 [num_envs] (NULL
+ * without a critic; may be NULL with one: the critic is then not evaluated).  action_out may be NULL when value_out is given (values
+ * only).  Allocates nothing, never synchronises, reads nothing of the envs' state and is hipGraph-capturable.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a wrong struct_size, n_hidden outside 1 .. 3, hidden outside 1 .. 128,
+ * an unknown activation, a head that is not the id's, a null weight or bias among the layers in use, a log_std missing (continuous)
+ * or given (discrete), a value_out without a critic, no output at all. */
+int sg_policy_act_device(sg_env *env, const sg_policy *policy, const float *obs_dev, uint64_t seed, uint64_t step,
+                         int32_t deterministic, void *action_out, float *logp_out, float *value_out, void *hip_stream);
+/* n_steps closed-loop steps without a host synchronisation.  obs float32 [n_steps + 1, num_envs, obs_dim]: the caller puts the
+ * current observations into row 0; step t reads row t and writes row t + 1.  action float32 [n_steps, num_envs, 2] (discrete ids:
+ * int32 [n_steps, num_envs]); logp (may be NULL), reward, done, truncated [n_steps, num_envs]; value float32 [n_steps + 1, num_envs].
+ * For every t the call enqueues the act kernel above with step = first_step + t and then the single step that sg_step_device
+ * enqueues, so episode statistics, normalization, reward profiles and counters behave exactly as for n_steps calls of
+ * sg_step_device, and every output is bit for bit what that hand-written loop gives.  Then one launch of the critic alone writes
+ * value[n_steps] -- sg_gae_device's last_value, its `value` being rows 0 .. n_steps - 1.
+ * terminal_list (may be NULL) is filled as by sg_rollout_device_terminal -- one record per finished env-step, `step` = t, the count
+ * running past the capacity, the excess dropped; nothing with auto_reset off -- and, when terminal_value (float32 [capacity]) is
+ * given too, one more launch of the critic over the list's records writes V of each record's observation beside it: count, step_env
+ * and terminal_value together are a ready sg_value_list.  With observation normalization on the records are normalized with the
+ * statistics of their own step, like sg_step_device's terminal_obs rows, and so are the rows the policy reads.
+ * Refused as sg_policy_act_device refuses, and: n_steps < 1, a null obs, action, reward, done or truncated, a value or
+ * terminal_value without a critic, a terminal_value without a terminal_list, an incomplete list.  (A critic with a NULL value is
+ * accepted: it is not evaluated for the rows; terminal_value is still served.) */
+int sg_rollout_policy_device(sg_env *env, int32_t n_steps, const sg_policy *policy, uint64_t seed, uint64_t first_step,
+                             int32_t deterministic, float *obs, void *action, float *logp, float *value, float *reward,
+                             uint8_t *done, uint8_t *truncated, const sg_terminal_list *terminal_list, float *terminal_value,
+                             void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

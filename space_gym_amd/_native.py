@@ -101,6 +101,17 @@ class SgPriorityDraw(C.Structure):
     _fields_ = [("index", C.c_void_p), ("cell", C.c_void_p), ("weight", C.c_void_p), ("leaf", C.c_void_p)]
 
 
+class SgPolicyMlp(C.Structure):
+    """sg_policy_mlp (include/spacegym.h): device pointers of one net's layers, torch.nn.Linear layout"""
+    _fields_ = [("weight", C.c_void_p * 4), ("bias", C.c_void_p * 4)]
+
+
+class SgPolicy(C.Structure):
+    """sg_policy (include/spacegym.h): a small MLP actor-critic whose parameters stay where the learner keeps them"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_hidden", C.c_int32), ("hidden", C.c_int32), ("activation", C.c_int32),
+                ("head", C.c_int32), ("reserved", C.c_int32), ("actor", SgPolicyMlp), ("critic", SgPolicyMlp), ("log_std", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -184,6 +195,9 @@ SYMBOLS = {
     "sg_priority_sample_config_init": (None, [C.POINTER(SgPrioritySampleConfig)]),
     "sg_priority_sample_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgPriority), C.POINTER(SgPrioritySampleConfig), C.c_int64,
                                             C.POINTER(SgPriorityDraw), _vp]),
+    "sg_policy_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
+    "sg_rollout_policy_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

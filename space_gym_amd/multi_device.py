@@ -134,6 +134,12 @@ class MultiDeviceVectorEnv:
 
     snapshot = snapshot_torch = restore = restore_torch = _no_snapshots
 
+    def _no_policy(self, *args, **kwargs):
+        raise NotImplementedError("policy_torch / policy_act_torch / rollout_policy_torch: single-device front end only, not served by "
+                                  "MultiDeviceVectorEnv (one SpaceGymVectorEnv per device runs a policy on its envs)")
+
+    policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
+
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)
         for all envs on the root device.  copy=False: the front end's own arrays, two sets that alternate (what a call returns

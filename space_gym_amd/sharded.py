@@ -134,6 +134,12 @@ class ShardedVectorEnv:
 
     snapshot = snapshot_torch = restore = restore_torch = _no_snapshots
 
+    def _no_policy(self, *args, **kwargs):
+        raise NotImplementedError("policy_torch / policy_act_torch / rollout_policy_torch: single-device front end only, not served by "
+                                  "ShardedVectorEnv (a rank's SpaceGymVectorEnv runs a policy on its envs)")
+
+    policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
+
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""
         tail = () if self.discrete else (2,)

@@ -124,6 +124,16 @@ class ReplayPriority:
         self.leaf, self.node, self.hdr = leaf, node, hdr
 
 
+class Policy:
+    """What policy_torch returns: the sg_policy struct (include/spacegym.h) over the caller's parameter tensors, which it keeps
+    alive; n_hidden, hidden, activation and has_critic describe the nets."""
+
+    def __init__(self, struct, tensors, has_critic):
+        self.struct, self.tensors, self.has_critic = struct, tuple(tensors), bool(has_critic)
+        self.n_hidden, self.hidden = int(struct.n_hidden), int(struct.hidden)
+        self.activation = "relu" if struct.activation else "tanh"
+
+
 class SpaceGymVectorEnv:
     metadata = {"render.modes": ["rgb_array"]}
 
@@ -1056,6 +1066,139 @@ class SpaceGymVectorEnv:
                                          ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(out["advantage"]),
                                          ptr(out["returns"]), self._stream()), "sg_gae_device")
         return out["advantage"], out["returns"]
+
+    # ------------------------------------------------------------------ actor-critic policy on the device, closed-loop rollouts
+    def policy_torch(self, actor, critic=None, log_std=None, activation="tanh"):
+        """A handle on a small MLP actor-critic whose parameters stay where they are (sg_policy: no copy, no transpose; what an
+        optimizer step writes is what the next call reads).  actor / critic: lists [(weight, bias), ...] of float32 CUDA tensors
+        in torch.nn.Linear layout -- 1 .. 3 hidden layers of one width (1 .. 128) and the head: obs_dim -> hidden -> ... -> 2
+        (continuous ids: the mean; log_std float32 [2] is needed) or 6 (discrete ids: the logits), the critic -> 1 (None: no
+        values).  Parameters of nn.Linear modules pass as they are: [(m.weight, m.bias) for m in linears].  activation: "tanh" or
+        "relu", after every hidden layer."""
+        import torch
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+        head = 6 if self.discrete else 2
+        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=1 if activation == "relu" else 0, head=head)
+        keep = []
+
+        def net(name, layers, out, mlp):
+            layers = [tuple(l) for l in layers]
+            n_hidden = len(layers) - 1
+            if not 1 <= n_hidden <= 3:
+                raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
+            w0 = layers[0][0]
+            if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
+                raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {self.obs_dim})")
+            hidden = int(w0.shape[0])
+            if not 1 <= hidden <= 128:
+                raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
+            fan_in = self.obs_dim
+            for l, (w, b) in enumerate(layers):
+                width = out if l == n_hidden else hidden
+                self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
+                self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
+                mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
+                keep.extend((w, b))
+                fan_in = hidden
+            return n_hidden, hidden
+
+        p.n_hidden, p.hidden = net("actor", actor, head, p.actor)
+        if critic is not None:
+            if net("critic", critic, 1, p.critic) != (p.n_hidden, p.hidden):
+                raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
+        if self.discrete:
+            if log_std is not None:
+                raise ValueError("log_std: the discrete ids take none")
+        else:
+            if log_std is None:
+                raise ValueError("log_std: a continuous id needs the float32 [2] log standard deviations")
+            self._check_tensor("log_std", log_std, torch.float32, (2,))
+            p.log_std = log_std.data_ptr()
+            keep.append(log_std)
+        return Policy(p, keep, critic is not None)
+
+    def policy_act_torch(self, policy, obs, seed=0, step=0, deterministic=False, out=None):
+        """(action, logp, value) of the observations obs float32 [B, D] under a policy_torch handle, in one launch on torch's
+        current stream (sg_policy_act_device: no host synchronisation, nothing allocated by the engine, graph-capturable).
+        action float32 [B, 2], unclamped (discrete ids: int32 [B]); logp float32 [B]; value float32 [B], None without a critic.
+        Env i's noise is a function of (seed, step, env_index_base + i); deterministic: the mean / the first argmax.
+        out: dict action / logp / value of tensors to fill (allocated when absent)."""
+        import torch
+        if not isinstance(policy, Policy):
+            raise ValueError("policy: expected the handle policy_torch returns")
+        B, D = self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (B, D))
+        if out is None:
+            out = dict(action=torch.empty((B,) if self.discrete else (B, 2), dtype=torch.int32 if self.discrete else torch.float32, device=obs.device),
+                       logp=torch.empty(B, dtype=torch.float32, device=obs.device),
+                       value=torch.empty(B, dtype=torch.float32, device=obs.device) if policy.has_critic else None)
+        else:
+            self._check_tensor("out['action']", out["action"], torch.int32 if self.discrete else torch.float32, (B,) if self.discrete else (B, 2))
+            self._check_tensor("out['logp']", out["logp"], torch.float32, (B,))
+            if out.get("value") is not None:
+                if not policy.has_critic:
+                    raise ValueError("out['value']: the policy has no critic")
+                self._check_tensor("out['value']", out["value"], torch.float32, (B,))
+        value = out.get("value")
+        self._ck(self._lib.sg_policy_act_device(self._h, C.byref(policy.struct), C.c_void_p(obs.data_ptr()), int(seed), int(step),
+                                                int(bool(deterministic)), C.c_void_p(out["action"].data_ptr()),
+                                                C.c_void_p(out["logp"].data_ptr()),
+                                                C.c_void_p(value.data_ptr()) if value is not None else None, self._stream()),
+                 "sg_policy_act_device")
+        return out["action"], out["logp"], value
+
+    def rollout_policy_torch(self, policy, obs, action, logp, value, reward, done, trunc, seed=0, first_step=0, deterministic=False,
+                             terminal=None):
+        """K closed-loop steps on torch's current stream without a host synchronisation (sg_rollout_policy_device): for every t the
+        policy acts on obs[t] (noise step first_step + t) and the env steps into obs[t + 1], exactly as policy_act_torch followed by
+        step_torch would.  obs float32 [K + 1, B, D] with the current observations in row 0; action float32 [K, B, 2] (discrete
+        ids: int32 [K, B]); logp, reward float32 / done, trunc uint8 [K, B]; value float32 [K + 1, B] (None without a critic): row K
+        is GAE's last_value.  terminal: a terminal_list_torch dict; it is filled like rollout_torch's and, with a critic,
+        terminal["value"] (float32 [capacity], made on first use) receives V of every record's observation, so that
+            env.gae_torch(reward, done, trunc, value[:-1], value[-1], terminal=env.value_list_torch(terminal, terminal["value"]))
+        needs nothing in between."""
+        import torch
+        if not isinstance(policy, Policy):
+            raise ValueError("policy: expected the handle policy_torch returns")
+        if not isinstance(action, torch.Tensor) or action.dim() < 2 or int(action.shape[0]) < 1:
+            raise ValueError("action: expected a CUDA tensor of at least one step")
+        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
+        if policy.has_critic and value is None:
+            raise ValueError("value: the policy has a critic; pass the float32 [K + 1, B] tensor its values go to")
+        if not policy.has_critic and value is not None:
+            raise ValueError("value: the policy has no critic")
+        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
+        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
+        self._check_tensor("logp", logp, torch.float32, (K, B))
+        if value is not None:
+            self._check_tensor("value", value, torch.float32, (K + 1, B))
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        tl, tv = None, None
+        if terminal is not None:
+            cap = int(terminal["step_env"].shape[0])
+            if (not isinstance(terminal["count"], torch.Tensor) or terminal["count"].dtype not in (torch.int32, torch.uint32)
+                    or terminal["count"].numel() != 1):
+                raise ValueError("terminal['count']: expected one 32-bit integer")
+            self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
+            self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
+            self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, D))
+            if policy.has_critic:
+                if terminal.get("value") is None:
+                    terminal["value"] = torch.empty(cap, dtype=torch.float32, device=terminal["obs"].device)
+                self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
+                tv = terminal["value"]
+            tl = _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_rollout_policy_device(self._h, K, C.byref(policy.struct), int(seed), int(first_step), int(bool(deterministic)),
+                                                    ptr(obs), ptr(action), ptr(logp), ptr(value), ptr(reward), ptr(done), ptr(trunc),
+                                                    C.byref(tl) if tl is not None else None, ptr(tv), self._stream()),
+                 "sg_rollout_policy_device")
+        return obs, action, logp, value, reward, done, trunc
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

@@ -780,6 +780,58 @@ int sg_rollout_policy_device(sg_env *env, int32_t n_steps, const sg_policy *poli
                              uint8_t *done, uint8_t *truncated, const sg_terminal_list *terminal_list, float *terminal_value,
                              void *hip_stream);
 
+/* The learner's half of an on-policy update: log-prob, entropy and value of GIVEN (obs, action) rows under the current parameters,
+ * and the gradients of a loss on those three vectors with respect to the parameters.  The loss itself stays the caller's code on
+ * [n] vectors; everything that touches the [n, hidden] activations is the engine's.  n is a row count of its own, any n >= 1 (a
+ * minibatch of the flattened rollout, not num_envs).
+ *   obs     float32 [n, obs_dim]
+ *   action  float32 [n, 2], unclamped as sg_policy_act_device stored it (discrete ids: int32 [n], 0 .. 5; any other value is the
+ *           caller's error -- the kernels select by comparison and never index with it, so it cannot reach out of bounds)
+ * Forward.  value, and the discrete logp, are sg_policy_act_device's arithmetic: for the rows and actions it produced they are its
+ * outputs bit for bit (exp(logp_new - logp_old) is exactly 1 before the first optimizer step).
+ *   continuous  z_d = (a_d - mean_d) exp(-log_std_d);  logp = sum_d(-z_d^2 / 2 - log_std_d - ln(2 pi) / 2)   (close to act's, which
+ *               scores its own eps, not bit-equal);  entropy = sum_d log_std_d + 1 + ln(2 pi), the same for every row
+ *   discrete    logp = (logit_a - max) - log(total);  entropy = -sum_j p_j log p_j of the softmax
+ * Every output is float32 [n] and may be NULL (the critic is not evaluated without value_out, the actor not without logp_out or
+ * entropy_out).  One launch; allocates nothing, never synchronises, hipGraph-capturable.
+ * Refused: whatever sg_policy_act_device refuses of the policy; n < 1; a null obs or action; no output; value_out without a critic. */
+int sg_policy_evaluate_device(sg_env *env, const sg_policy *policy, int64_t n, const float *obs, const void *action, float *logp_out,
+                              float *entropy_out, float *value_out, void *hip_stream);
+/* Writable float32 device pointers, one per parameter of an sg_policy and of its shape */
+typedef struct sg_policy_grads_mlp {
+    float *weight[4];
+    float *bias[4];
+} sg_policy_grads_mlp;
+typedef struct sg_policy_grads {
+    uint32_t struct_size;  /* sizeof(sg_policy_grads) */
+    uint32_t reserved;     /* 0 */
+    sg_policy_grads_mlp actor;
+    sg_policy_grads_mlp critic;  /* may be all NULL when g_value is NULL; given without g_value it is written with zeros */
+    float *log_std;              /* [2], continuous ids; must be NULL for the discrete ids */
+} sg_policy_grads;
+/* grads = sum_i (g_logp[i] d logp_i + g_entropy[i] d entropy_i + g_value[i] d value_i) / d theta for every parameter theta: WRITTEN,
+ * not accumulated.  g_* float32 [n], the loss's gradients by the three outputs of sg_policy_evaluate_device; each may be NULL (zeros).
+ * There is no gradient with respect to obs or action.
+ *   continuous  d logp / d mean_d = z_d / sigma_d;  d logp / d log_std_d = z_d^2 - 1;  d entropy / d log_std_d = 1
+ *   discrete    d logp / d logit_j = [j = a] - p_j;  d entropy / d logit_j = -p_j (log p_j + H)
+ *   tanh' = 1 - h^2 of the activation h;  relu' = [pre-activation > 0]: 0 at 0, as torch.
+ * The forward pass is recomputed inside the backward launch: no [n, hidden] activation goes to memory between the two calls.
+ * Two launches: the backward, whose workgroups leave partial sums in `workspace` (at least sg_policy_grad_workspace_bytes(env,
+ * policy, n) bytes of device memory, any content), and a reduction of the partials in workgroup order.  Allocates nothing, never
+ * synchronises, hipGraph-capturable.
+ * Arithmetic: float32 throughout, no floating-point atomics, a fixed summation order over the rows -- two calls with the same
+ * inputs and the same n give bit-identical gradients.  The order is a function of n (how rows group into workgroups), so the same
+ * rows inside a batch of another n may round differently; the forward outputs have no such dependence.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): whatever sg_policy_act_device refuses of the policy; n < 1; a null obs
+ * or action; a null grads, a wrong struct_size or reserved; a null pointer among the gradient slots in use (the actor's layers,
+ * log_std for the continuous ids, the critic's layers when g_value is given); a log_std gradient for a discrete id; a null workspace
+ * or one smaller than the query's answer; g_value or critic gradients given for a policy without a critic. */
+int sg_policy_grad_device(sg_env *env, const sg_policy *policy, int64_t n, const float *obs, const void *action, const float *g_logp,
+                          const float *g_entropy, const float *g_value, const sg_policy_grads *grads, void *workspace,
+                          size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_policy_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid policy or n */
+size_t sg_policy_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int64_t n);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

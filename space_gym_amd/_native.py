@@ -112,6 +112,11 @@ class SgPolicy(C.Structure):
                 ("head", C.c_int32), ("reserved", C.c_int32), ("actor", SgPolicyMlp), ("critic", SgPolicyMlp), ("log_std", C.c_void_p)]
 
 
+class SgPolicyGrads(C.Structure):
+    """sg_policy_grads (include/spacegym.h): where sg_policy_grad_device writes the gradient of every parameter of an sg_policy"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("actor", SgPolicyMlp), ("critic", SgPolicyMlp), ("log_std", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -198,6 +203,9 @@ SYMBOLS = {
     "sg_policy_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
     "sg_rollout_policy_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),
+    "sg_policy_evaluate_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_policy_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
+    "sg_policy_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int64]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

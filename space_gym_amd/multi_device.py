@@ -139,6 +139,7 @@ class MultiDeviceVectorEnv:
                                   "MultiDeviceVectorEnv (one SpaceGymVectorEnv per device runs a policy on its envs)")
 
     policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
+    policy_evaluate_torch = policy_evaluate_raw_torch = policy_grad_torch = _no_policy
 
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)

@@ -139,6 +139,7 @@ class ShardedVectorEnv:
                                   "ShardedVectorEnv (a rank's SpaceGymVectorEnv runs a policy on its envs)")
 
     policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
+    policy_evaluate_torch = policy_evaluate_raw_torch = policy_grad_torch = _no_policy
 
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""

@@ -132,6 +132,45 @@ class Policy:
         self.struct, self.tensors, self.has_critic = struct, tuple(tensors), bool(has_critic)
         self.n_hidden, self.hidden = int(struct.n_hidden), int(struct.hidden)
         self.activation = "relu" if struct.activation else "tanh"
+        self.workspace = None  # policy_grad_torch's partial sums: a uint8 tensor, grown on demand
+
+
+_POLICY_EVALUATE = None
+
+
+def _policy_evaluate_function():
+    """the torch.autograd.Function behind policy_evaluate_torch (made on first use: torch is imported lazily)"""
+    global _POLICY_EVALUATE
+    if _POLICY_EVALUATE is not None:
+        return _POLICY_EVALUATE
+    import torch
+
+    class PolicyEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, policy, obs, action, *params):
+            ctx.env, ctx.policy = env, policy
+            ctx.save_for_backward(obs, action)
+            logp, entropy, value = env.policy_evaluate_raw_torch(policy, obs, action)
+            if value is None:
+                return logp, entropy, None
+            return logp, entropy, value
+
+        @staticmethod
+        def backward(ctx, g_logp, g_entropy, g_value=None):
+            env, policy = ctx.env, ctx.policy
+            obs, action = ctx.saved_tensors
+            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            out = env.policy_grad_torch(policy, obs, action, con(g_logp), con(g_entropy), con(g_value) if policy.has_critic else None)
+            L = policy.n_hidden + 1
+            grads = [t for pair in out["actor"] for t in pair]
+            if policy.has_critic:
+                grads += [t for pair in out["critic"] for t in pair] if out["critic"] is not None else [None] * (2 * L)
+            if out["log_std"] is not None:
+                grads.append(out["log_std"])
+            return (None, None, None, None, *grads)
+
+    _POLICY_EVALUATE = PolicyEvaluate
+    return PolicyEvaluate
 
 
 class SpaceGymVectorEnv:
@@ -1199,6 +1238,122 @@ class SpaceGymVectorEnv:
                                                     C.byref(tl) if tl is not None else None, ptr(tv), self._stream()),
                  "sg_rollout_policy_device")
         return obs, action, logp, value, reward, done, trunc
+
+    # ------------------------------------------------------------------ the learner's half: evaluate given actions, parameter gradients
+    def _policy_rows(self, policy, obs, action):
+        """checks (policy, obs [n, D], action [n, 2] / int32 [n]) and returns n"""
+        import torch
+        if not isinstance(policy, Policy):
+            raise ValueError("policy: expected the handle policy_torch returns")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
+        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (n,) if self.discrete else (n, 2))
+        return n
+
+    def policy_evaluate_raw_torch(self, policy, obs, action, out=None):
+        """(logp, entropy, value) float32 [n] of the given rows -- obs float32 [n, D], action float32 [n, 2] as policy_act_torch stored
+        it (discrete ids: int32 [n]) -- under a policy_torch handle: one launch on torch's current stream, no autograd
+        (sg_policy_evaluate_device; graph-capturable).  n is the caller's: a minibatch of the flattened rollout.  value and the discrete
+        logp are policy_act_torch's bit for bit.  out: dict logp / entropy / value of tensors to fill (allocated when None; an entry
+        that is absent or None is not computed).  value is None without a critic."""
+        import torch
+        n = self._policy_rows(policy, obs, action)
+        if out is None:
+            out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in (("logp", "entropy", "value") if policy.has_critic else ("logp", "entropy"))}
+        else:
+            if out.get("value") is not None and not policy.has_critic:
+                raise ValueError("out['value']: the policy has no critic")
+            if all(out.get(k) is None for k in ("logp", "entropy", "value")):
+                raise ValueError("out: expected at least one of logp, entropy, value")
+            for k in ("logp", "entropy", "value"):
+                if out.get(k) is not None:
+                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_policy_evaluate_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(action), ptr(out.get("logp")),
+                                                     ptr(out.get("entropy")), ptr(out.get("value")), self._stream()), "sg_policy_evaluate_device")
+        return out.get("logp"), out.get("entropy"), out.get("value")
+
+    def _policy_grad_workspace(self, policy, n, device):
+        """the workspace tensor cached on the handle, grown when n needs more -- never inside a capture"""
+        import torch
+        need = int(self._lib.sg_policy_grad_workspace_bytes(self._h, C.byref(policy.struct), n))
+        if need == 0:
+            self._ck(-1, "sg_policy_grad_workspace_bytes")
+        ws = policy.workspace
+        if ws is None or ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError(f"policy_grad_torch: the workspace ({0 if ws is None else ws.numel()} bytes) is too small for n = {n} ({need} bytes) "
+                                 "and cannot be allocated during a graph capture: make one warm-up call with this n before capturing")
+            ws = policy.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def policy_grad_torch(self, policy, obs, action, g_logp=None, g_entropy=None, g_value=None, out=None):
+        """Gradients of a loss with respect to the policy's parameters, given the loss's gradients g_logp / g_entropy / g_value
+        (float32 [n], None: zeros) by policy_evaluate_raw_torch's outputs at the same (obs, action): sg_policy_grad_device, two
+        launches on torch's current stream, the forward pass recomputed inside, graph-capturable after one warm-up call with the same
+        n (which sizes the workspace kept on the handle).  Returns a dict actor / critic (lists of (weight, bias) gradients, critic
+        None without g_value) / log_std (None for the discrete ids), WRITTEN, not accumulated; out: such a dict of tensors to fill.
+        Same inputs and same n: the same bits."""
+        import torch
+        n = self._policy_rows(policy, obs, action)
+        for name, g in (("g_logp", g_logp), ("g_entropy", g_entropy), ("g_value", g_value)):
+            if g is not None:
+                self._check_tensor(name, g, torch.float32, (n,))
+        if g_value is not None and not policy.has_critic:
+            raise ValueError("g_value: the policy has no critic")
+        L = policy.n_hidden + 1
+        params = policy.tensors
+        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if policy.has_critic else ()
+        if out is None:
+            pairs = lambda ts: [(torch.empty_like(ts[2 * l]), torch.empty_like(ts[2 * l + 1])) for l in range(L)]
+            out = dict(actor=pairs(a_par), critic=pairs(c_par) if g_value is not None else None,
+                       log_std=None if self.discrete else torch.empty_like(params[-1]))
+        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+
+        def fill(name, mlp, pairs, like):
+            pairs = [tuple(x) for x in pairs]
+            if len(pairs) != L:
+                raise ValueError(f"out['{name}']: expected {L} (weight, bias) pairs, got {len(pairs)}")
+            for l, (w, b) in enumerate(pairs):
+                self._check_tensor(f"out['{name}'][{l}] weight", w, torch.float32, tuple(like[2 * l].shape))
+                self._check_tensor(f"out['{name}'][{l}] bias", b, torch.float32, tuple(like[2 * l + 1].shape))
+                mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
+
+        fill("actor", g.actor, out["actor"], a_par)
+        if out.get("critic") is not None:
+            if not policy.has_critic:
+                raise ValueError("out['critic']: the policy has no critic")
+            fill("critic", g.critic, out["critic"], c_par)
+        elif g_value is not None:
+            raise ValueError("out['critic']: g_value is given; the critic's gradients need tensors")
+        if self.discrete:
+            if out.get("log_std") is not None:
+                raise ValueError("out['log_std']: the discrete ids have none")
+        else:
+            if out.get("log_std") is None:
+                raise ValueError("out['log_std']: expected a float32 [2] tensor")
+            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
+            g.log_std = out["log_std"].data_ptr()
+        ws = self._policy_grad_workspace(policy, n, obs.device)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_policy_grad_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(action), ptr(g_logp), ptr(g_entropy),
+                                                 ptr(g_value), C.byref(g), ptr(ws), ws.numel(), self._stream()), "sg_policy_grad_device")
+        return out
+
+    def policy_evaluate_torch(self, policy, obs, action):
+        """logp, entropy, value = the scores of the stored (obs, action) rows under the CURRENT parameters, differentiable with respect
+        to the parameter tensors the handle holds: a torch.autograd.Function whose forward is policy_evaluate_raw_torch and whose
+        backward is policy_grad_torch (no [n, hidden] activation is kept between the two; obs and action get no gradient).  Write
+        the loss in torch on the three [n] vectors and call backward(): the parameters' .grad accumulate as usual.  Under
+        torch.no_grad(), or when no parameter requires grad, it is the plain forward.  value is None without a critic."""
+        self._policy_rows(policy, obs, action)
+        return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

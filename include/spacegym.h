@@ -832,6 +832,76 @@ int sg_policy_grad_device(sg_env *env, const sg_policy *policy, int64_t n, const
 /* Bytes of workspace sg_policy_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid policy or n */
 size_t sg_policy_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int64_t n);
 
+/* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
+ * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
+ * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.
+ *   critic c   x = [obs[0 .. obs_dim) | action[0 .. 2)]:  obs_dim + 2 -> hidden (x n_hidden) -> 1
+ * Every hidden layer is followed by the activation; the head is linear.  Parameters are float32 DEVICE pointers in torch.nn.Linear
+ * layout (weight[0] is [hidden, obs_dim + 2]), owned by the caller and read in place at every call, like sg_policy's; a target
+ * network is simply a second sg_qnet.  The action is used AS GIVEN: nothing here clamps it -- the caller decides whether a critic
+ * sees the stored unclamped action or a clamped one.  Arithmetic: sg_policy's -- float32 throughout, output neuron j starts at b[j]
+ * and takes fmaf(W[j][k], x[k], .) for k = 0, 1, ..., one row per lane, no atomics: a row's Q depends on that row and the parameters
+ * only.  tests/q_model.py states all of it in NumPy; DESIGN section 19 has the kernels and the tolerances. */
+typedef struct sg_qnet {
+    uint32_t struct_size;  /* sizeof(sg_qnet) */
+    int32_t n_critics;     /* 1 or 2 */
+    int32_t n_hidden;      /* hidden layers of each critic, 1 .. 3 */
+    int32_t hidden;        /* their width, 1 .. 128 */
+    int32_t activation;    /* SG_POLICY_TANH / SG_POLICY_RELU */
+    sg_policy_mlp critic[2];  /* critic[1] is ignored when n_critics is 1 */
+} sg_qnet;
+/* q1_out, q2_out float32 [n] = Q_1, Q_2 of the rows obs float32 [n, obs_dim], action float32 [n, 2], any n >= 1, in ONE launch on the
+ * stream, one critic after the other.  Either may be NULL (that critic is not evaluated), not both; q2_out needs n_critics == 2.
+ * Allocates nothing, never synchronises, hipGraph-capturable.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a discrete id; a null qnet or a wrong struct_size; n_critics outside
+ * 1 .. 2, n_hidden outside 1 .. 3, hidden outside 1 .. 128, an unknown activation; a null weight or bias among the layers in use;
+ * n < 1; a null obs or action; no output; q2_out with one critic. */
+int sg_q_evaluate_device(sg_env *env, const sg_qnet *qnet, int64_t n, const float *obs, const float *action, float *q1_out,
+                         float *q2_out, void *hip_stream);
+/* Writable float32 device pointers, one per parameter of an sg_qnet and of its shape */
+typedef struct sg_qnet_grads {
+    uint32_t struct_size;  /* sizeof(sg_qnet_grads) */
+    uint32_t reserved;     /* 0 */
+    sg_policy_grads_mlp critic[2];  /* a critic's slots may be all NULL when its g_q is NULL; given without it they are written with zeros */
+} sg_qnet_grads;
+/* g_q1, g_q2 float32 [n]: the loss's gradients by the two outputs of sg_q_evaluate_device; each may be NULL (zeros).
+ *   grads         receives sum_i g_qc[i] d Q_c[i] / d theta for every weight and bias of critic c: WRITTEN, not accumulated.  NULL: the
+ *                 critics are frozen and only the action gradient is wanted; then no weight-gradient work and no reduction is enqueued
+ *                 and the workspace is not looked at.
+ *   g_action_out  float32 [n, 2], may be NULL: receives sum_c g_qc[i] d Q_c[i] / d action[i], critic 1's term added to critic 0's.  Per
+ *                 row, no reduction over the batch: a function of the row, its g values and the parameters only -- it does not depend
+ *                 on n, on the row's position or on whether grads is given (same bits).
+ * tanh' = 1 - h^2 of the activation h; relu' = [pre-activation > 0]: 0 at 0, as torch.  The forward pass is recomputed inside the
+ * launch.  With grads: two launches, the backward, whose workgroups leave partial sums in `workspace` (at least
+ * sg_q_grad_workspace_bytes(env, qnet, n) bytes of device memory, any content), and a reduction of the partials in workgroup order;
+ * float32 throughout, no atomics, a fixed summation order over the rows that is a function of n: the same inputs and the same n give
+ * the same bits.  Allocates nothing, never synchronises, hipGraph-capturable.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): whatever sg_q_evaluate_device refuses of the qnet and the rows; g_q2, or
+ * gradient slots of critic 1, with one critic; neither grads nor g_action_out; a wrong struct_size or reserved of grads; a null
+ * pointer among the slots of a critic whose g_q is given; with grads, a null workspace or one smaller than the query's answer. */
+int sg_q_grad_device(sg_env *env, const sg_qnet *qnet, int64_t n, const float *obs, const float *action, const float *g_q1,
+                     const float *g_q2, const sg_qnet_grads *grads, float *g_action_out, void *workspace, size_t workspace_bytes,
+                     void *hip_stream);
+/* Bytes of workspace sg_q_grad_device needs for n rows when grads is given (it grows with n up to a cap); 0 and an error message for
+ * an invalid qnet or n */
+size_t sg_q_grad_workspace_bytes(sg_env *env, const sg_qnet *qnet, int64_t n);
+/* The actor's side of the chain, on an sg_policy of a continuous id (a discrete id is refused; the policy's critic is not used).
+ * action_out float32 [n, 2] = mean(obs) + exp(log_std) * eps for the rows obs float32 [n, obs_dim] and the caller's noise eps float32
+ * [n, 2], UNCLAMPED.  eps NULL: the mean -- for the same rows bit for bit sg_policy_act_device's deterministic action; exp(log_std) is
+ * that kernel's own expression.  One launch; allocates nothing, never synchronises, hipGraph-capturable.
+ * Refused: whatever sg_policy_act_device refuses of the policy; a discrete id; n < 1; a null obs or action_out. */
+int sg_policy_action_device(sg_env *env, const sg_policy *policy, int64_t n, const float *obs, const float *eps, float *action_out,
+                            void *hip_stream);
+/* grads->actor and grads->log_std receive sum_i sum_d g_action[i][d] d action[i][d] / d theta, g_action float32 [n, 2] (e.g.
+ * sg_q_grad_device's g_action_out times the loss's sign): d a_d / d mean_d = 1, d a_d / d log_std_d = exp(log_std_d) eps[i][d] (0 with
+ * a NULL eps).  WRITTEN, not accumulated; grads->critic is neither read nor written.  sg_policy_grad_device's two launches with another
+ * score: the same workspace (sg_policy_grad_workspace_bytes(env, policy, n)), reduction and determinism.
+ * Refused: whatever sg_policy_action_device refuses of the policy and the rows; a null g_action or grads, a wrong struct_size or
+ * reserved; a null pointer among the actor's slots or log_std; a null workspace or one smaller than the query's answer. */
+int sg_policy_action_grad_device(sg_env *env, const sg_policy *policy, int64_t n, const float *obs, const float *eps,
+                                 const float *g_action, const sg_policy_grads *grads, void *workspace, size_t workspace_bytes,
+                                 void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

@@ -117,6 +117,17 @@ class SgPolicyGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("actor", SgPolicyMlp), ("critic", SgPolicyMlp), ("log_std", C.c_void_p)]
 
 
+class SgQnet(C.Structure):
+    """sg_qnet (include/spacegym.h): one or two Q critics on [obs | action] rows, parameters read where the learner keeps them"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_critics", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32),
+                ("activation", C.c_int32), ("critic", SgPolicyMlp * 2)]
+
+
+class SgQnetGrads(C.Structure):
+    """sg_qnet_grads (include/spacegym.h): where sg_q_grad_device writes the gradient of every parameter of an sg_qnet"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("critic", SgPolicyMlp * 2)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -206,6 +217,11 @@ SYMBOLS = {
     "sg_policy_evaluate_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_policy_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
     "sg_policy_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int64]),
+    "sg_q_evaluate_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "sg_q_grad_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgQnetGrads), _vp, _vp, C.c_size_t, _vp]),
+    "sg_q_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgQnet), C.c_int64]),
+    "sg_policy_action_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp]),
+    "sg_policy_action_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

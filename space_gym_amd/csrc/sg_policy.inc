@@ -85,13 +85,19 @@ __device__ __forceinline__ void policy_layer(const float *__restrict__ wt, const
     }
 }
 
-// One net for this lane's observation row: head outputs 0 .. kPolicyHeadPad - 1 into `out`
+// One net for this lane's observation row: head outputs 0 .. kPolicyHeadPad - 1 into `out`.  tail (the Q critics, sg_qnet.inc): the
+// last kPolicyActDim of the p.obs_dim inputs are tail[0 .. 1], the row's action, and obs_row holds the others
 template <int NT>
 __device__ __forceinline__ void policy_net(const PolicyDev &p, const PolicyNet &net, int head, const float *__restrict__ obs_row,
-                                           float *wt, float *bs, float *h, float (&out)[kPolicyHeadPad]) {
+                                           float *wt, float *bs, float *h, float (&out)[kPolicyHeadPad], const float *__restrict__ tail = nullptr) {
     constexpr int J = kPolicyTile * NT;
     const int stride = (int)blockDim.x;
-    for (int k = 0; k < p.obs_dim; k++) h[(size_t)k * stride] = obs_row[k];
+    const int from_obs = tail ? p.obs_dim - kPolicyActDim : p.obs_dim;
+    for (int k = 0; k < from_obs; k++) h[(size_t)k * stride] = obs_row[k];
+    if (tail) {
+#pragma unroll
+        for (int d = 0; d < kPolicyActDim; d++) h[(size_t)(from_obs + d) * stride] = tail[d];
+    }
     int in = p.obs_dim;
     for (int l = 0; l < p.n_hidden; l++) {  // (wave-uniform)
         policy_stage<J>(wt, bs, net.w[l], net.b[l], in, p.hidden);

@@ -135,15 +135,16 @@ __global__ __launch_bounds__(policy_block(NT)) void policy_evaluate_kernel(Polic
     if (entropy_out) entropy_out[i] = s.entropy;
 }
 
-// ws[j][k] = W[j][k0 + k] (k0 + k < in, j < out; else 0) for k < 32, bs = 0: the weights as policy_layer wants them for dh = W^T dz
+// ws[j][k] = W[j][k0 + k] (k0 + k < in, j < out; else 0) for k < J, bs = 0: the weights as policy_layer<J> wants them for dh = W^T dz
+template <int J>
 __device__ __forceinline__ void policy_stage_plain(float *__restrict__ ws, float *__restrict__ bs, const float *__restrict__ W, int in, int out,
                                                    int k0) {
     __syncthreads();
-    for (int idx = (int)threadIdx.x; idx < out * kPolicyGradChunk; idx += (int)blockDim.x) {
-        const int j = idx >> 5, k = idx & 31;
-        ws[j * (kPolicyGradChunk + kPolicyRowPad) + k] = k0 + k < in ? W[(size_t)j * in + k0 + k] : 0.0f;
+    for (int idx = (int)threadIdx.x; idx < out * J; idx += (int)blockDim.x) {
+        const int j = idx / J, k = idx % J;  // (J is a power of two)
+        ws[j * (J + kPolicyRowPad) + k] = k0 + k < in ? W[(size_t)j * in + k0 + k] : 0.0f;
     }
-    if (threadIdx.x < kPolicyGradChunk) bs[threadIdx.x] = 0.0f;
+    if (threadIdx.x < J) bs[threadIdx.x] = 0.0f;
     __syncthreads();
 }
 
@@ -192,18 +193,30 @@ __device__ __forceinline__ void policy_grad_weights(const float *__restrict__ dz
     }
 }
 
-// which: 0 the actor, 1 the critic.  gl, ge, gv: this row's loss gradients (0 for the idle lanes of the last tile)
-template <int NT>
-__device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, const float *__restrict__ obs_row, const void *__restrict__ action,
-                                                int i, float gl, float ge, float gv, const PolicyGradLayout &lay, float *__restrict__ part,
-                                                bool first, float *wt, float *bs, float *store) {
+// One net of a row tile: forward into the store, then the walk down.
+//   which    0 the actor, 1 the critic (sg_qnet.inc: critic 0 / 1): the net and its offsets in `lay`;  head: its outputs
+//   extra    rows of the head's dz past `head` whose bias column is a sum of its own (the continuous actor: 2, d loss / d log_std_d)
+//   tail     NULL, or the row's action: the last kPolicyActDim of the p.obs_dim inputs (obs_row holds the others)
+//   head_dz  (head outputs, dz [kPolicyHeadPad]): fills this row's dz of the head's outputs and extra rows, zeros elsewhere (zeros
+//            altogether for the idle lanes of the last tile)
+//   weights  false: the parameters' sums are not wanted, no MFMA runs and `part` is not touched
+//   want_dx  dx receives W0[:, in - 2 .. in)^T dz0, this row's gradient by the tail (else dx is left as it is)
+template <int NT, typename HeadDz>
+__device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, int head, int extra, const float *__restrict__ obs_row,
+                                                const float *__restrict__ tail, HeadDz head_dz, const PolicyGradLayout &lay,
+                                                float *__restrict__ part, bool first, bool weights, bool want_dx, float (&dx)[kPolicyActDim], float *wt,
+                                                float *bs, float *store) {
     constexpr int C = kPolicyGradChunk;
     const PolicyNet &net = which ? p.critic : p.actor;
     const int R = (int)blockDim.x, S = R + 2, tid = (int)threadIdx.x, D = p.obs_dim, H = p.hidden, L = p.n_hidden;
-    const int head = which ? 1 : p.head;
+    const int from_obs = tail ? D - kPolicyActDim : D;
     __syncthreads();  // the store is free: every wave has finished the net before
-    for (int k = 0; k < D; k++) store[(size_t)k * S + tid] = obs_row[k];
-    // rows of the store: [0, D) the observation, [D + l H, D + (l + 1) H) hidden layer l, then kPolicyHeadPad rows for the head's dz
+    for (int k = 0; k < from_obs; k++) store[(size_t)k * S + tid] = obs_row[k];
+    if (tail) {
+#pragma unroll
+        for (int d = 0; d < kPolicyActDim; d++) store[(size_t)(from_obs + d) * S + tid] = tail[d];
+    }
+    // rows of the store: [0, D) the input row, [D + l H, D + (l + 1) H) hidden layer l, then kPolicyHeadPad rows for the head's dz
     int in = D;
     const float *hin = store + tid;
     for (int l = 0; l < L; l++) {
@@ -221,33 +234,36 @@ __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, c
         hin = hout;
         in = H;
     }
-    float out[kPolicyHeadPad];
+    float out[kPolicyHeadPad], dz_head[kPolicyHeadPad];
     policy_stage<kPolicyHeadPad>(wt, bs, net.w[L], net.b[L], in, head);
     policy_layer<kPolicyHeadPad>(wt, bs, hin, S, in, out);
-    PolicyScore s;
-    if (which) {
-#pragma unroll
-        for (int j = 0; j < kPolicyHeadPad; j++) s.dz[j] = 0.0f;
-        s.dz[0] = gv;
-    } else {
-        policy_score(p, out, action, i, gl, ge, true, s);
-    }
+    head_dz(out, dz_head);
     float *hd = store + (size_t)(D + L * H) * S;
 #pragma unroll
-    for (int j = 0; j < kPolicyHeadPad; j++) hd[(size_t)j * S + tid] = s.dz[j];
-    const int extra = (!which && !p.discrete) ? kPolicyActDim : 0;  // the log_std rows of the continuous head
+    for (int j = 0; j < kPolicyHeadPad; j++) hd[(size_t)j * S + tid] = dz_head[j];
     for (int l = L; l >= 0; l--) {
         const int out_l = l == L ? head : H, in_l = l == 0 ? D : H;
         const float *dz = l == L ? hd : store + (size_t)(D + l * H) * S;
         float *hprev = l == 0 ? store : store + (size_t)(D + (l - 1) * H) * S;
         __syncthreads();  // dz of every row of the tile is in LDS
-        policy_grad_weights(dz, hprev, S, R, out_l, out_l + (l == L ? extra : 0), in_l, part + lay.w[which][l], part + lay.b[which][l],
-                            part + lay.log_std, first);
-        if (l == 0) break;
+        if (weights)
+            policy_grad_weights(dz, hprev, S, R, out_l, out_l + (l == L ? extra : 0), in_l, part + lay.w[which][l], part + lay.b[which][l],
+                                part + lay.log_std, first);
+        if (l == 0) {
+            if (want_dx) {  // one step further, for the tail's two columns of W0 only (out_l = H rows of the staging area: it holds max(H, D))
+                constexpr int A = 4;  // kPolicyActDim padded to policy_layer's four outputs
+                policy_stage_plain<A>(wt, bs, net.w[0], in_l, out_l, in_l - kPolicyActDim);
+                float acc[A];
+                policy_layer<A>(wt, bs, dz + tid, S, out_l, acc);
+#pragma unroll
+                for (int d = 0; d < kPolicyActDim; d++) dx[d] = acc[d];
+            }
+            break;
+        }
 #pragma unroll
         for (int c = 0; c < NT; c++) {
             if (c * C >= in_l) break;  // (uniform)
-            policy_stage_plain(wt, bs, net.w[l], in_l, out_l, c * C);  // (its first barrier: every wave is past the MFMA reads of hprev)
+            policy_stage_plain<C>(wt, bs, net.w[l], in_l, out_l, c * C);  // (its first barrier: every wave is past the MFMA reads of hprev)
             float acc[C];
             policy_layer<C>(wt, bs, dz + tid, S, out_l, acc);
 #pragma unroll
@@ -281,8 +297,22 @@ __global__ __launch_bounds__(policy_grad_block(NT)) void policy_grad_kernel(Poli
         const int row = live ? i : n - 1;  // idle lanes of the last tile redo its last row with zero loss gradients
         const float *obs_row = obs + (size_t)row * p.obs_dim;
         const float gl = live && g_logp ? g_logp[i] : 0.0f, ge = live && g_entropy ? g_entropy[i] : 0.0f;
-        if (g_value) policy_grad_net<NT>(p, 1, obs_row, action, row, 0.0f, 0.0f, live ? g_value[i] : 0.0f, lay, part, first, wt, bs, store);
-        policy_grad_net<NT>(p, 0, obs_row, action, row, gl, ge, 0.0f, lay, part, first, wt, bs, store);
+        float no_dx[kPolicyActDim];  // (no gradient by the input row here)
+        if (g_value) {
+            const float gv = live ? g_value[i] : 0.0f;
+            policy_grad_net<NT>(p, 1, 1, 0, obs_row, nullptr, [&](const float (&)[kPolicyHeadPad], float (&dz)[kPolicyHeadPad]) {
+#pragma unroll
+                for (int j = 0; j < kPolicyHeadPad; j++) dz[j] = 0.0f;
+                dz[0] = gv;
+            }, lay, part, first, true, false, no_dx, wt, bs, store);
+        }
+        policy_grad_net<NT>(p, 0, p.head, p.discrete ? 0 : kPolicyActDim, obs_row, nullptr,
+                            [&](const float (&out)[kPolicyHeadPad], float (&dz)[kPolicyHeadPad]) {
+            PolicyScore s;
+            policy_score(p, out, action, row, gl, ge, true, s);
+#pragma unroll
+            for (int j = 0; j < kPolicyHeadPad; j++) dz[j] = s.dz[j];
+        }, lay, part, first, true, false, no_dx, wt, bs, store);
         first = false;
     }
 }

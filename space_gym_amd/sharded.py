@@ -140,6 +140,8 @@ class ShardedVectorEnv:
 
     policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
     policy_evaluate_torch = policy_evaluate_raw_torch = policy_grad_torch = _no_policy
+    q_torch = q_evaluate_torch = q_evaluate_raw_torch = q_grad_torch = _no_policy
+    policy_action_torch = policy_action_raw_torch = policy_action_grad_torch = _no_policy
 
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""

@@ -135,7 +135,89 @@ class Policy:
         self.workspace = None  # policy_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
+class QNet:
+    """What q_torch returns: the sg_qnet struct (include/spacegym.h) over the caller's parameter tensors, which it keeps alive --
+    critic 0's (weight, bias) pairs, then critic 1's; n_critics, n_hidden, hidden and activation describe the nets."""
+
+    def __init__(self, struct, tensors):
+        self.struct, self.tensors = struct, tuple(tensors)
+        self.n_critics, self.n_hidden, self.hidden = int(struct.n_critics), int(struct.n_hidden), int(struct.hidden)
+        self.activation = "relu" if struct.activation else "tanh"
+        self.workspace = None  # q_grad_torch's partial sums: a uint8 tensor, grown on demand
+
+
 _POLICY_EVALUATE = None
+_Q_EVALUATE = None
+_POLICY_ACTION = None
+
+
+def _q_evaluate_function():
+    """the torch.autograd.Function behind q_evaluate_torch (made on first use: torch is imported lazily)"""
+    global _Q_EVALUATE
+    if _Q_EVALUATE is not None:
+        return _Q_EVALUATE
+    import torch
+
+    class QEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, q, obs, action, *params):
+            ctx.env, ctx.q = env, q
+            ctx.save_for_backward(obs, action)
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: that critic is skipped
+            return env.q_evaluate_raw_torch(q, obs, action)
+
+        @staticmethod
+        def backward(ctx, g_q1, g_q2=None):
+            env, q = ctx.env, ctx.q
+            obs, action = ctx.saved_tensors
+            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            want_params, want_action = any(ctx.needs_input_grad[4:]), ctx.needs_input_grad[3]
+            out = env.q_grad_torch(q, obs, action, con(g_q1), con(g_q2) if q.n_critics == 2 else None, params=want_params,
+                                   action_grad=want_action)
+            L = q.n_hidden + 1
+            grads = [None] * (2 * L * q.n_critics)
+            if want_params:
+                grads = [t for pairs in out["critics"] for pair in pairs for t in pair]
+            return (None, None, None, out["action"], *grads)
+
+    _Q_EVALUATE = QEvaluate
+    return QEvaluate
+
+
+def _policy_action_function():
+    """the torch.autograd.Function behind policy_action_torch"""
+    global _POLICY_ACTION
+    if _POLICY_ACTION is not None:
+        return _POLICY_ACTION
+    import torch
+
+    class PolicyAction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, policy, obs, eps, *params):
+            ctx.env, ctx.policy, ctx.has_eps = env, policy, eps is not None
+            ctx.save_for_backward(*((obs, eps) if eps is not None else (obs,)))
+            return env.policy_action_raw_torch(policy, obs, eps)
+
+        @staticmethod
+        def backward(ctx, g_action):
+            env, policy = ctx.env, ctx.policy
+            if g_action is None:
+                return (None,) * (4 + len(policy.tensors))
+            obs = ctx.saved_tensors[0]
+            eps = ctx.saved_tensors[1] if ctx.has_eps else None
+            L = policy.n_hidden + 1
+            none = [None] * (len(policy.tensors))
+            if not any(ctx.needs_input_grad[4:]):
+                return (None, None, None, None, *none)
+            out = env.policy_action_grad_torch(policy, obs, g_action.to(torch.float32).contiguous(), eps)
+            grads = [t for pair in out["actor"] for t in pair]
+            if policy.has_critic:
+                grads += [None] * (2 * L)
+            grads.append(out["log_std"])
+            return (None, None, None, None, *grads)
+
+    _POLICY_ACTION = PolicyAction
+    return PolicyAction
 
 
 def _policy_evaluate_function():
@@ -1354,6 +1436,233 @@ class SpaceGymVectorEnv:
         torch.no_grad(), or when no parameter requires grad, it is the plain forward.  value is None without a critic."""
         self._policy_rows(policy, obs, action)
         return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
+
+    # ------------------------------------------------------------------ the off-policy learner's nets: twin Q critics, action gradients
+    def q_torch(self, critics, activation="relu"):
+        """A handle on one or two Q critics whose parameters stay where they are (sg_qnet: no copy, no transpose; a target network
+        is a second handle).  critics: a list of one or two nets, each a list [(weight, bias), ...] of float32 CUDA tensors in
+        torch.nn.Linear layout -- obs_dim + 2 -> hidden (1 .. 3 layers of one width 1 .. 128) -> 1, on the row [obs | action].
+        Continuous ids only.  The action is used as given: nothing clamps it."""
+        import torch
+        if self.discrete:
+            raise ValueError("q_torch: the Q critics take the continuous ids' 2-vector action; the discrete ids are not served")
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+        critics = [list(c) for c in critics]
+        if not 1 <= len(critics) <= 2:
+            raise ValueError(f"critics: expected one or two nets, got {len(critics)}")
+        q = _native.SgQnet(struct_size=C.sizeof(_native.SgQnet), n_critics=len(critics), activation=1 if activation == "relu" else 0)
+        keep, shapes = [], []
+        for c, layers in enumerate(critics):
+            name = f"critics[{c}]"
+            layers = [tuple(l) for l in layers]
+            n_hidden = len(layers) - 1
+            if not 1 <= n_hidden <= 3:
+                raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
+            w0 = layers[0][0]
+            if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
+                raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {self.obs_dim + 2})")
+            hidden = int(w0.shape[0])
+            if not 1 <= hidden <= 128:
+                raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
+            fan_in = self.obs_dim + 2
+            for l, (w, b) in enumerate(layers):
+                width = 1 if l == n_hidden else hidden
+                self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
+                self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
+                q.critic[c].weight[l], q.critic[c].bias[l] = w.data_ptr(), b.data_ptr()
+                keep.extend((w, b))
+                fan_in = hidden
+            shapes.append((n_hidden, hidden))
+        if len(set(shapes)) != 1:
+            raise ValueError(f"critics[1]: expected {shapes[0][0]} hidden layers of width {shapes[0][1]}, like critics[0]")
+        q.n_hidden, q.hidden = shapes[0]
+        return QNet(q, keep)
+
+    def _q_rows(self, q, obs, action):
+        """checks (q, obs [n, D], action [n, 2]) and returns n"""
+        import torch
+        if not isinstance(q, QNet):
+            raise ValueError("q: expected the handle q_torch returns")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
+        self._check_tensor("action", action, torch.float32, (n, 2))
+        return n
+
+    def q_evaluate_raw_torch(self, q, obs, action, out=None):
+        """(q1, q2) float32 [n] of the rows obs float32 [n, D], action float32 [n, 2] under a q_torch handle; q2 is None with one
+        critic.  One launch on torch's current stream, no host synchronisation, no autograd (sg_q_evaluate_device; graph-capturable).
+        out: dict q1 / q2 of tensors to fill (allocated when None; an entry that is absent or None is not computed)."""
+        import torch
+        n = self._q_rows(q, obs, action)
+        if out is None:
+            out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in ("q1", "q2")[:q.n_critics]}
+        else:
+            if out.get("q2") is not None and q.n_critics != 2:
+                raise ValueError("out['q2']: the handle has one critic")
+            if out.get("q1") is None and out.get("q2") is None:
+                raise ValueError("out: expected at least one of q1, q2")
+            for k in ("q1", "q2"):
+                if out.get(k) is not None:
+                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_q_evaluate_device(self._h, C.byref(q.struct), n, ptr(obs), ptr(action), ptr(out.get("q1")), ptr(out.get("q2")),
+                                                self._stream()), "sg_q_evaluate_device")
+        return out.get("q1"), out.get("q2")
+
+    def _grad_workspace(self, handle, need, n, device, who):
+        """the workspace tensor cached on a Policy / QNet handle, grown when n needs more -- never inside a capture"""
+        import torch
+        if need == 0:
+            self._ck(-1, who)
+        ws = handle.workspace
+        if ws is None or ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError(f"{who}: the workspace ({0 if ws is None else ws.numel()} bytes) is too small for n = {n} ({need} bytes) "
+                                 "and cannot be allocated during a graph capture: make one warm-up call with this n before capturing")
+            ws = handle.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def q_grad_torch(self, q, obs, action, g_q1=None, g_q2=None, params=True, action_grad=False, out=None):
+        """The critics' half of a backward pass, given the loss's gradients g_q1 / g_q2 (float32 [n], None: zeros) by
+        q_evaluate_raw_torch's outputs at the same (obs, action): sg_q_grad_device on torch's current stream, the forward pass
+        recomputed inside.  Returns dict critics / action:
+          critics  (params) per critic the list of (weight, bias) gradients, WRITTEN, not accumulated (zeros for a critic whose g is
+                   None); None with params=False: the critics are frozen, no weight-gradient work is done
+          action   (action_grad) float32 [n, 2] = sum_c g_qc[i] dQ_c[i] / d action[i]: per row, the same bits for any n and for
+                   params on or off; None otherwise
+        out: such a dict of tensors to fill.  With params the call is graph-capturable after one warm-up call with the same n (which
+        sizes the workspace kept on the handle).  Same inputs and same n: the same bits."""
+        import torch
+        n = self._q_rows(q, obs, action)
+        for name, g in (("g_q1", g_q1), ("g_q2", g_q2)):
+            if g is not None:
+                self._check_tensor(name, g, torch.float32, (n,))
+        if g_q2 is not None and q.n_critics != 2:
+            raise ValueError("g_q2: the handle has one critic")
+        if not params and not action_grad:
+            raise ValueError("q_grad_torch: nothing to compute (params and action_grad are both off)")
+        L = q.n_hidden + 1
+        like = [q.tensors[2 * L * c:2 * L * (c + 1)] for c in range(q.n_critics)]
+        if out is None:
+            out = dict(critics=[[(torch.empty_like(ts[2 * l]), torch.empty_like(ts[2 * l + 1])) for l in range(L)] for ts in like] if params else None,
+                       action=torch.empty((n, 2), dtype=torch.float32, device=obs.device) if action_grad else None)
+        else:
+            if params and out.get("critics") is None:
+                raise ValueError("out['critics']: params is on; the critics' gradients need tensors")
+            if action_grad and out.get("action") is None:
+                raise ValueError("out['action']: action_grad is on; expected a float32 [n, 2] tensor")
+            out = dict(critics=out.get("critics") if params else None, action=out.get("action") if action_grad else None)
+        g, ws = None, None
+        if params:
+            g = _native.SgQnetGrads(struct_size=C.sizeof(_native.SgQnetGrads))
+            nets = [list(c) for c in out["critics"]]
+            if len(nets) != q.n_critics:
+                raise ValueError(f"out['critics']: expected {q.n_critics} nets, got {len(nets)}")
+            for c, pairs in enumerate(nets):
+                pairs = [tuple(x) for x in pairs]
+                if len(pairs) != L:
+                    raise ValueError(f"out['critics'][{c}]: expected {L} (weight, bias) pairs, got {len(pairs)}")
+                for l, (w, b) in enumerate(pairs):
+                    self._check_tensor(f"out['critics'][{c}][{l}] weight", w, torch.float32, tuple(like[c][2 * l].shape))
+                    self._check_tensor(f"out['critics'][{c}][{l}] bias", b, torch.float32, tuple(like[c][2 * l + 1].shape))
+                    g.critic[c].weight[l], g.critic[c].bias[l] = w.data_ptr(), b.data_ptr()
+        if action_grad:
+            self._check_tensor("out['action']", out["action"], torch.float32, (n, 2))
+        if params:
+            ws = self._grad_workspace(q, int(self._lib.sg_q_grad_workspace_bytes(self._h, C.byref(q.struct), n)), n, obs.device, "q_grad_torch")
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_q_grad_device(self._h, C.byref(q.struct), n, ptr(obs), ptr(action), ptr(g_q1), ptr(g_q2),
+                                            C.byref(g) if g is not None else None, ptr(out["action"]), ptr(ws),
+                                            ws.numel() if ws is not None else 0, self._stream()), "sg_q_grad_device")
+        return out
+
+    def q_evaluate_torch(self, q, obs, action):
+        """q1, q2 = the critics' values of the (obs, action) rows under the CURRENT parameters, differentiable with respect to the
+        parameter tensors the handle holds and, when action.requires_grad, with respect to action (obs gets None): a
+        torch.autograd.Function whose forward is q_evaluate_raw_torch and whose backward is ONE q_grad_torch call -- params off when
+        no parameter needs a gradient, action_grad only when the action needs one.  q2 is None with one critic.  With
+        policy_action_torch it makes a TD3 / DDPG update plain torch on [n] vectors."""
+        self._q_rows(q, obs, action)
+        return _q_evaluate_function().apply(self, q, obs, action, *q.tensors)
+
+    def _policy_action_rows(self, policy, obs, eps, who):
+        import torch
+        if not isinstance(policy, Policy):
+            raise ValueError("policy: expected the handle policy_torch returns")
+        if self.discrete:
+            raise ValueError(f"{who}: a = mean + exp(log_std) eps needs a continuous id; the discrete ids are not served")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
+        if eps is not None:
+            self._check_tensor("eps", eps, torch.float32, (n, 2))
+        return n
+
+    def policy_action_raw_torch(self, policy, obs, eps=None, out=None):
+        """action float32 [n, 2] = mean(obs) + exp(log_std) * eps under a policy_torch handle of a continuous id, unclamped; eps
+        float32 [n, 2] is the caller's noise, None: the mean (policy_act_torch(deterministic=True)'s action bit for bit).  One launch
+        on torch's current stream, no autograd (sg_policy_action_device; graph-capturable).  out: the tensor to fill."""
+        import torch
+        n = self._policy_action_rows(policy, obs, eps, "policy_action_raw_torch")
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=obs.device)
+        else:
+            self._check_tensor("out", out, torch.float32, (n, 2))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_policy_action_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(eps), ptr(out), self._stream()),
+                 "sg_policy_action_device")
+        return out
+
+    def policy_action_grad_torch(self, policy, obs, g_action, eps=None, out=None):
+        """Gradients of a loss with respect to the actor's parameters and log_std through policy_action_raw_torch's action, given the
+        loss's gradient g_action float32 [n, 2] by it (e.g. q_grad_torch's `action`): sg_policy_action_grad_device, policy_grad_torch's
+        two launches with another score and its workspace.  Returns dict actor (list of (weight, bias) gradients) / log_std, WRITTEN,
+        not accumulated; the policy's critic is not involved.  out: such a dict of tensors to fill."""
+        import torch
+        n = self._policy_action_rows(policy, obs, eps, "policy_action_grad_torch")
+        self._check_tensor("g_action", g_action, torch.float32, (n, 2))
+        L = policy.n_hidden + 1
+        a_par = policy.tensors[:2 * L]
+        if out is None:
+            out = dict(actor=[(torch.empty_like(a_par[2 * l]), torch.empty_like(a_par[2 * l + 1])) for l in range(L)],
+                       log_std=torch.empty_like(policy.tensors[-1]))
+        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+        pairs = [tuple(x) for x in out["actor"]]
+        if len(pairs) != L:
+            raise ValueError(f"out['actor']: expected {L} (weight, bias) pairs, got {len(pairs)}")
+        for l, (w, b) in enumerate(pairs):
+            self._check_tensor(f"out['actor'][{l}] weight", w, torch.float32, tuple(a_par[2 * l].shape))
+            self._check_tensor(f"out['actor'][{l}] bias", b, torch.float32, tuple(a_par[2 * l + 1].shape))
+            g.actor.weight[l], g.actor.bias[l] = w.data_ptr(), b.data_ptr()
+        if out.get("log_std") is None:
+            raise ValueError("out['log_std']: expected a float32 [2] tensor")
+        self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
+        g.log_std = out["log_std"].data_ptr()
+        ws = self._grad_workspace(policy, int(self._lib.sg_policy_grad_workspace_bytes(self._h, C.byref(policy.struct), n)), n, obs.device,
+                                  "policy_action_grad_torch")
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_policy_action_grad_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(eps), ptr(g_action), C.byref(g), ptr(ws),
+                                                        ws.numel(), self._stream()), "sg_policy_action_grad_device")
+        return out
+
+    def policy_action_torch(self, policy, obs, eps=None):
+        """action = mean(obs) + exp(log_std) * eps (eps None: the mean), differentiable with respect to the actor's tensors and log_std
+        of the handle: a torch.autograd.Function over policy_action_raw_torch / policy_action_grad_torch.  obs and eps get None.  The
+        action is unclamped; clamp it in torch where the algorithm wants that."""
+        self._policy_action_rows(policy, obs, eps, "policy_action_torch")
+        return _policy_action_function().apply(self, policy, obs, eps, *policy.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

@@ -902,6 +902,83 @@ int sg_policy_action_grad_device(sg_env *env, const sg_policy *policy, int64_t n
                                  const float *g_action, const sg_policy_grads *grads, void *workspace, size_t workspace_bytes,
                                  void *hip_stream);
 
+/* The SAC actor: a Gaussian whose mean AND log_std depend on the state, squashed by tanh, with its log-prob (Jacobian term included)
+ * and the reparametrised gradients of (action, logp) by the actor's parameters.  Continuous ids only (a discrete id is refused with a
+ * message); the continuous ids clamp actions to [-1, 1]^2 on the device, so tanh needs no action scale.  The reference has no
+ * counterpart.
+ *   actor   obs_dim -> hidden (x n_hidden) -> 4     head outputs 0, 1: mean_d;  outputs 2, 3: raw_d (the unclamped log_std)
+ * Parameters are float32 DEVICE pointers in torch.nn.Linear layout (the head is [4, hidden]), owned by the caller and read in place at
+ * every call, like sg_policy's.  Per row, for d = 0, 1:
+ *   ls_d  = min(max(raw_d, log_std_min), log_std_max)           (torch.clamp; SB3 uses -20, 2)
+ *   u_d   = mean_d + exp(ls_d) * eps_d
+ *   e_d   = exp(-2 |u_d|)
+ *   a_d   = sign(u_d) (1 - e_d) / (1 + e_d)                     (= tanh u_d)
+ *   ldj_d = 2 (ln 2 - |u_d| - log1p(e_d))                       (= log(1 - a_d^2), exact: finite when a_d rounds to +-1)
+ *   logp  = sum_d(-eps_d^2 / 2 - ls_d - ln(2 pi) / 2 - ldj_d)
+ * This is the log-prob of torch.distributions.TransformedDistribution(Normal, TanhTransform).  It is NOT SB3's log(1 - a^2 + 1e-6),
+ * which loses all its digits in float32 once 1 - a^2 is near 1e-6 and caps the correction instead of following it.
+ * Gradients treat eps as a constant (reparametrisation).  With g_action [n, 2] and g_logp [n], the loss's gradients by the outputs:
+ *   gu_d      = g_action_d * 4 e_d / (1 + e_d)^2 + g_logp * 2 a_d
+ *   dz_mean_d = gu_d
+ *   dz_raw_d  = (gu_d * exp(ls_d) * eps_d - g_logp) * [log_std_min <= raw_d <= log_std_max]     (bounds inclusive, as torch.clamp's backward)
+ * Arithmetic: sg_policy's -- float32 throughout, output neuron j starts at b[j] and takes fmaf(W[j][k], h[k], .) for k = 0, 1, ...,
+ * one row per lane; exp(ls), log1p and the Box-Muller are the precise library forms, e_d the fast exponential the tanh activation
+ * uses.  Every call takes the stream, allocates nothing, never synchronises and is hipGraph-capturable.
+ * tests/squashed_model.py states all of it in NumPy float64; DESIGN section 20 has the kernels and the tolerances. */
+typedef struct sg_squashed_policy {
+    uint32_t struct_size;  /* sizeof(sg_squashed_policy) */
+    int32_t n_hidden;      /* hidden layers, 1 .. 3 */
+    int32_t hidden;        /* their width, 1 .. 128 */
+    int32_t activation;    /* SG_POLICY_TANH / SG_POLICY_RELU */
+    float log_std_min;     /* the clamp of raw_d; finite, log_std_min <= log_std_max */
+    float log_std_max;
+    sg_policy_mlp actor;   /* the head is [4, hidden] */
+    int32_t reserved;      /* 0 */
+} sg_squashed_policy;
+/* (action, logp) of the observation rows obs_dev float32 [num_envs, obs_dim] in ONE launch: action_out float32 [num_envs, 2] in
+ * [-1, 1]; logp_out float32 [num_envs], may be NULL.  eps is the Box-Muller pair of one Philox block, key = seed, counter =
+ * (env_index_base + i, step lo, step hi, 6) -- stream tag 6, after sg_policy's 5; deterministic != 0: eps = 0, nothing drawn.  Env i's
+ * results depend on its row, the parameters and (seed, step, env_index_base + i) only.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a discrete id; a null policy or a wrong struct_size or reserved; n_hidden
+ * outside 1 .. 3, hidden outside 1 .. 128, an unknown activation; log_std_min > log_std_max or a bound that is not finite; a null weight
+ * or bias among the layers in use; a null obs or action_out. */
+int sg_squashed_act_device(sg_env *env, const sg_squashed_policy *sp, const float *obs_dev, uint64_t seed, uint64_t step,
+                           int32_t deterministic, float *action_out, float *logp_out, void *hip_stream);
+/* The same with the caller's noise eps float32 [n, 2] on rows obs float32 [n, obs_dim], any n >= 1 -- the update's actor loss, and the
+ * critic target's (a', logp') on next_obs.  eps NULL: zeros; for the same rows bit for bit the deterministic sg_squashed_act_device.
+ * One launch.  Refused: whatever sg_squashed_act_device refuses of the policy; n < 1; a null obs or action_out. */
+int sg_squashed_sample_device(sg_env *env, const sg_squashed_policy *sp, int64_t n, const float *obs, const float *eps,
+                              float *action_out, float *logp_out, void *hip_stream);
+typedef struct sg_squashed_grads {
+    uint32_t struct_size;  /* sizeof(sg_squashed_grads) */
+    uint32_t reserved;     /* 0 */
+    sg_policy_grads_mlp actor;
+} sg_squashed_grads;
+/* grads->actor receives sum_i (g_action[i] . d action[i] + g_logp[i] d logp[i]) / d theta for every weight and bias: WRITTEN, not
+ * accumulated.  g_action float32 [n, 2] and g_logp float32 [n] are the loss's gradients by sg_squashed_sample_device's outputs at the
+ * same (obs, eps); each may be NULL (zeros), not both.  The forward pass is recomputed inside the launch.  Two launches, exactly
+ * sg_policy_grad_device's scheme: the backward, whose workgroups leave partial sums in `workspace` (at least
+ * sg_squashed_grad_workspace_bytes(env, sp, n) bytes of device memory, any content), and a reduction of the partials in workgroup
+ * order; no atomics, a fixed summation order that is a function of n: the same inputs and the same n give the same bits.
+ * Refused: whatever sg_squashed_sample_device refuses of the policy and the rows; both g NULL; a null grads, a wrong struct_size or
+ * reserved; a null pointer among the actor's slots in use; a null workspace or one smaller than the query's answer. */
+int sg_squashed_grad_device(sg_env *env, const sg_squashed_policy *sp, int64_t n, const float *obs, const float *eps,
+                            const float *g_action, const float *g_logp, const sg_squashed_grads *grads, void *workspace,
+                            size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_squashed_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid
+ * policy or n */
+size_t sg_squashed_grad_workspace_bytes(sg_env *env, const sg_squashed_policy *sp, int64_t n);
+/* n_steps closed-loop steps without a host synchronisation: sg_rollout_policy_device's loop with sg_squashed_act_device and no critic.
+ * obs float32 [n_steps + 1, num_envs, obs_dim] with the current observations in row 0; action float32 [n_steps, num_envs, 2]; logp (may
+ * be NULL), reward, done, truncated [n_steps, num_envs].  For every t the call enqueues the act kernel with step = first_step + t, then
+ * the single step sg_step_device enqueues, then the terminal list's records (terminal_list may be NULL; filled as by
+ * sg_rollout_policy_device): every output is bit for bit what that hand-written loop gives, with normalization on as well.  The
+ * buffers may be a replay ring's rows.
+ * Refused as sg_squashed_act_device refuses, and: n_steps < 1, a null obs, action, reward, done or truncated, an incomplete list. */
+int sg_rollout_squashed_device(sg_env *env, int32_t n_steps, const sg_squashed_policy *sp, uint64_t seed, uint64_t first_step,
+                               int32_t deterministic, float *obs, float *action, float *logp, float *reward, uint8_t *done,
+                               uint8_t *truncated, const sg_terminal_list *terminal_list, void *hip_stream);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

@@ -128,6 +128,17 @@ class SgQnetGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("critic", SgPolicyMlp * 2)]
 
 
+class SgSquashedPolicy(C.Structure):
+    """sg_squashed_policy (include/spacegym.h): the SAC actor -- a tanh-squashed Gaussian whose head gives mean and raw log_std"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_hidden", C.c_int32), ("hidden", C.c_int32), ("activation", C.c_int32),
+                ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("actor", SgPolicyMlp), ("reserved", C.c_int32)]
+
+
+class SgSquashedGrads(C.Structure):
+    """sg_squashed_grads (include/spacegym.h): where sg_squashed_grad_device writes the gradient of every parameter of the actor"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("actor", SgPolicyMlp)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -222,6 +233,13 @@ SYMBOLS = {
     "sg_q_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgQnet), C.c_int64]),
     "sg_policy_action_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp]),
     "sg_policy_action_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
+    "sg_squashed_act_device": (C.c_int, [_vp, C.POINTER(SgSquashedPolicy), _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp]),
+    "sg_squashed_sample_device": (C.c_int, [_vp, C.POINTER(SgSquashedPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "sg_squashed_grad_device": (C.c_int, [_vp, C.POINTER(SgSquashedPolicy), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgSquashedGrads), _vp,
+                                          C.c_size_t, _vp]),
+    "sg_squashed_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgSquashedPolicy), C.c_int64]),
+    "sg_rollout_squashed_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgSquashedPolicy), C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, C.POINTER(SgTerminalList), _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -146,9 +146,58 @@ class QNet:
         self.workspace = None  # q_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
+def _ptr(t):
+    """a tensor's device pointer as a ctypes argument; None stays NULL"""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class SquashedPolicy:
+    """What squashed_policy_torch returns: the sg_squashed_policy struct (include/spacegym.h) over the caller's actor tensors, which
+    it keeps alive; n_hidden, hidden, activation and log_std_bounds describe the net."""
+
+    def __init__(self, struct, tensors):
+        self.struct, self.tensors = struct, tuple(tensors)
+        self.n_hidden, self.hidden = int(struct.n_hidden), int(struct.hidden)
+        self.activation = "relu" if struct.activation else "tanh"
+        self.log_std_bounds = (float(struct.log_std_min), float(struct.log_std_max))
+        self.workspace = None  # squashed_grad_torch's partial sums: a uint8 tensor, grown on demand
+
+
 _POLICY_EVALUATE = None
 _Q_EVALUATE = None
 _POLICY_ACTION = None
+_SQUASHED_SAMPLE = None
+
+
+def _squashed_sample_function():
+    """the torch.autograd.Function behind squashed_sample_torch"""
+    global _SQUASHED_SAMPLE
+    if _SQUASHED_SAMPLE is not None:
+        return _SQUASHED_SAMPLE
+    import torch
+
+    class SquashedSample(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, sp, obs, eps, *params):
+            ctx.env, ctx.sp, ctx.has_eps = env, sp, eps is not None
+            ctx.save_for_backward(*((obs, eps) if eps is not None else (obs,)))
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
+            return env.squashed_sample_raw_torch(sp, obs, eps)
+
+        @staticmethod
+        def backward(ctx, g_action, g_logp):
+            env, sp = ctx.env, ctx.sp
+            none = (None,) * (4 + len(sp.tensors))
+            if (g_action is None and g_logp is None) or not any(ctx.needs_input_grad[4:]):
+                return none
+            obs = ctx.saved_tensors[0]
+            eps = ctx.saved_tensors[1] if ctx.has_eps else None
+            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            out = env.squashed_grad_torch(sp, obs, eps, con(g_action), con(g_logp))
+            return (None, None, None, None, *[t for pair in out["actor"] for t in pair])
+
+    _SQUASHED_SAMPLE = SquashedSample
+    return SquashedSample
 
 
 def _q_evaluate_function():
@@ -1269,6 +1318,22 @@ class SpaceGymVectorEnv:
                  "sg_policy_act_device")
         return out["action"], out["logp"], value
 
+    def _terminal_list_struct(self, terminal):
+        """checks a terminal_list_torch dict and returns (its sg_terminal_list, its capacity): shared by the closed-loop rollouts"""
+        import torch
+        for k in ("count", "step_env", "obs"):
+            if not isinstance(terminal.get(k), torch.Tensor):
+                raise ValueError(f"terminal['{k}']: expected a CUDA tensor (terminal_list_torch makes the dict)")
+        if terminal["count"].dtype not in (torch.int32, torch.uint32) or terminal["count"].numel() != 1:
+            raise ValueError("terminal['count']: expected one 32-bit integer")
+        if terminal["step_env"].dim() != 2:
+            raise ValueError("terminal['step_env']: expected an int32 tensor of shape (capacity, 2)")
+        cap = int(terminal["step_env"].shape[0])
+        self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
+        self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
+        self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, self.obs_dim))
+        return _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap), cap
+
     def rollout_policy_torch(self, policy, obs, action, logp, value, reward, done, trunc, seed=0, first_step=0, deterministic=False,
                              terminal=None):
         """K closed-loop steps on torch's current stream without a host synchronisation (sg_rollout_policy_device): for every t the
@@ -1299,19 +1364,12 @@ class SpaceGymVectorEnv:
         self._check_tensor("trunc", trunc, torch.uint8, (K, B))
         tl, tv = None, None
         if terminal is not None:
-            cap = int(terminal["step_env"].shape[0])
-            if (not isinstance(terminal["count"], torch.Tensor) or terminal["count"].dtype not in (torch.int32, torch.uint32)
-                    or terminal["count"].numel() != 1):
-                raise ValueError("terminal['count']: expected one 32-bit integer")
-            self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
-            self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
-            self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, D))
+            tl, cap = self._terminal_list_struct(terminal)
             if policy.has_critic:
                 if terminal.get("value") is None:
                     terminal["value"] = torch.empty(cap, dtype=torch.float32, device=terminal["obs"].device)
                 self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
                 tv = terminal["value"]
-            tl = _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap)
 
         def ptr(t):
             return C.c_void_p(t.data_ptr()) if t is not None else None
@@ -1515,7 +1573,7 @@ class SpaceGymVectorEnv:
         return out.get("q1"), out.get("q2")
 
     def _grad_workspace(self, handle, need, n, device, who):
-        """the workspace tensor cached on a Policy / QNet handle, grown when n needs more -- never inside a capture"""
+        """the workspace tensor cached on a Policy / QNet / SquashedPolicy handle, grown when n needs more -- never inside a capture"""
         import torch
         if need == 0:
             self._ck(-1, who)
@@ -1663,6 +1721,169 @@ class SpaceGymVectorEnv:
         action is unclamped; clamp it in torch where the algorithm wants that."""
         self._policy_action_rows(policy, obs, eps, "policy_action_torch")
         return _policy_action_function().apply(self, policy, obs, eps, *policy.tensors)
+
+    # ------------------------------------------------------------------ the SAC actor: tanh-squashed Gaussian, state-dependent log_std
+    def squashed_policy_torch(self, actor, log_std_bounds=(-20.0, 2.0), activation="relu"):
+        """A handle on a SAC actor whose parameters stay where they are (sg_squashed_policy: no copy, no transpose).  actor: a list
+        [(weight, bias), ...] of float32 CUDA tensors in torch.nn.Linear layout -- obs_dim -> hidden (1 .. 3 layers of one width
+        1 .. 128) -> 4: head outputs 0, 1 are the mean, 2, 3 the raw log_std, clamped to log_std_bounds (SB3's -20, 2).  The action
+        is tanh(mean + exp(log_std) eps) in [-1, 1]^2, logp the squashed Gaussian's.  Continuous ids only."""
+        import math
+
+        import torch
+        if self.discrete:
+            raise ValueError("squashed_policy_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        if activation not in ("tanh", "relu"):
+            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+        try:
+            lo, hi = (float(x) for x in log_std_bounds)
+        except (TypeError, ValueError):
+            raise ValueError(f"log_std_bounds: expected (min, max), got {log_std_bounds!r}") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"log_std_bounds: expected finite min <= max, got {log_std_bounds!r}")
+        p = _native.SgSquashedPolicy(struct_size=C.sizeof(_native.SgSquashedPolicy), activation=1 if activation == "relu" else 0,
+                                     log_std_min=lo, log_std_max=hi)
+        layers = [tuple(l) for l in actor]
+        n_hidden = len(layers) - 1
+        if not 1 <= n_hidden <= 3:
+            raise ValueError(f"actor: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
+        w0 = layers[0][0]
+        if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
+            raise ValueError(f"actor[0]: expected a weight of shape (hidden, {self.obs_dim})")
+        hidden = int(w0.shape[0])
+        if not 1 <= hidden <= 128:
+            raise ValueError(f"actor: hidden must be 1 .. 128, got {hidden}")
+        keep, fan_in = [], self.obs_dim
+        for l, (w, b) in enumerate(layers):
+            width = 4 if l == n_hidden else hidden
+            self._check_tensor(f"actor[{l}] weight", w, torch.float32, (width, fan_in))
+            self._check_tensor(f"actor[{l}] bias", b, torch.float32, (width,))
+            p.actor.weight[l], p.actor.bias[l] = w.data_ptr(), b.data_ptr()
+            keep.extend((w, b))
+            fan_in = hidden
+        p.n_hidden, p.hidden = n_hidden, hidden
+        return SquashedPolicy(p, keep)
+
+    def _squashed_rows(self, sp, obs, eps, who):
+        """checks (sp, obs [n, D], eps [n, 2] or None) and returns n"""
+        import torch
+        if not isinstance(sp, SquashedPolicy):
+            raise ValueError("sp: expected the handle squashed_policy_torch returns")
+        if self.discrete:
+            raise ValueError(f"{who}: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
+        if eps is not None:
+            self._check_tensor("eps", eps, torch.float32, (n, 2))
+        return n
+
+    def _squashed_out(self, out, n, device):
+        import torch
+        if out is None:
+            return dict(action=torch.empty((n, 2), dtype=torch.float32, device=device), logp=torch.empty(n, dtype=torch.float32, device=device))
+        if out.get("action") is None:
+            raise ValueError("out['action']: expected a float32 [n, 2] tensor")
+        self._check_tensor("out['action']", out["action"], torch.float32, (n, 2))
+        if out.get("logp") is not None:
+            self._check_tensor("out['logp']", out["logp"], torch.float32, (n,))
+        return out
+
+    def squashed_act_torch(self, sp, obs, seed=0, step=0, deterministic=False, out=None):
+        """(action, logp) of the observations obs float32 [B, D] under a squashed_policy_torch handle, in one launch on torch's current
+        stream (sg_squashed_act_device; graph-capturable).  action float32 [B, 2] in [-1, 1]; logp float32 [B].  Env i's noise is a
+        function of (seed, step, env_index_base + i); deterministic: tanh(mean).  out: dict action / logp of tensors to fill (logp
+        absent or None: not computed)."""
+        import torch
+        if not isinstance(sp, SquashedPolicy):
+            raise ValueError("sp: expected the handle squashed_policy_torch returns")
+        if self.discrete:
+            raise ValueError("squashed_act_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        B, D = self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (B, D))
+        out = self._squashed_out(out, B, obs.device)
+        self._ck(self._lib.sg_squashed_act_device(self._h, C.byref(sp.struct), _ptr(obs), int(seed), int(step), int(bool(deterministic)),
+                                                  _ptr(out["action"]), _ptr(out.get("logp")), self._stream()), "sg_squashed_act_device")
+        return out["action"], out.get("logp")
+
+    def rollout_squashed_torch(self, sp, obs, action, reward, done, trunc, logp=None, seed=0, first_step=0, deterministic=False, terminal=None):
+        """K closed-loop steps on torch's current stream without a host synchronisation (sg_rollout_squashed_device): for every t the
+        actor acts on obs[t] (noise step first_step + t) and the env steps into obs[t + 1], exactly as squashed_act_torch followed by
+        step_torch would.  obs float32 [K + 1, B, D] with the current observations in row 0; action float32 [K, B, 2]; reward float32 /
+        done, trunc uint8 [K, B]; logp float32 [K, B] or None.  terminal: a terminal_list_torch dict, filled like rollout_torch's.  The
+        buffers may be a replay ring's rows(K)."""
+        import torch
+        if not isinstance(sp, SquashedPolicy):
+            raise ValueError("sp: expected the handle squashed_policy_torch returns")
+        if self.discrete:
+            raise ValueError("rollout_squashed_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        if not isinstance(action, torch.Tensor) or action.dim() != 3 or int(action.shape[0]) < 1:
+            raise ValueError("action: expected a CUDA tensor [K, B, 2] of at least one step")
+        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
+        self._check_tensor("action", action, torch.float32, (K, B, 2))
+        if logp is not None:
+            self._check_tensor("logp", logp, torch.float32, (K, B))
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
+        self._ck(self._lib.sg_rollout_squashed_device(self._h, K, C.byref(sp.struct), int(seed), int(first_step), int(bool(deterministic)),
+                                                      _ptr(obs), _ptr(action), _ptr(logp), _ptr(reward), _ptr(done), _ptr(trunc),
+                                                      C.byref(tl) if tl is not None else None, self._stream()), "sg_rollout_squashed_device")
+        return obs, action, logp, reward, done, trunc
+
+    def squashed_sample_raw_torch(self, sp, obs, eps=None, out=None):
+        """(action, logp) of the rows obs float32 [n, D] with the caller's noise eps float32 [n, 2] (None: zeros -- for the same rows
+        squashed_act_torch(deterministic=True) bit for bit), any n >= 1: one launch on torch's current stream, no autograd
+        (sg_squashed_sample_device; graph-capturable).  out: dict action / logp of tensors to fill (logp absent or None: not computed)."""
+        n = self._squashed_rows(sp, obs, eps, "squashed_sample_raw_torch")
+        out = self._squashed_out(out, n, obs.device)
+        self._ck(self._lib.sg_squashed_sample_device(self._h, C.byref(sp.struct), n, _ptr(obs), _ptr(eps), _ptr(out["action"]), _ptr(out.get("logp")),
+                                                     self._stream()), "sg_squashed_sample_device")
+        return out["action"], out.get("logp")
+
+    def squashed_grad_torch(self, sp, obs, eps=None, g_action=None, g_logp=None, out=None):
+        """Gradients of a loss with respect to the actor's parameters through squashed_sample_raw_torch's (action, logp) at the same
+        (obs, eps), given the loss's gradients g_action float32 [n, 2] and g_logp float32 [n] by them (each may be None: zeros, not
+        both): sg_squashed_grad_device, two launches on torch's current stream, the forward pass recomputed inside, graph-capturable
+        after one warm-up call with the same n (which sizes the workspace kept on the handle).  Returns dict actor: the list of
+        (weight, bias) gradients, WRITTEN, not accumulated; out: such a dict of tensors to fill.  Same inputs and same n: the same bits."""
+        import torch
+        n = self._squashed_rows(sp, obs, eps, "squashed_grad_torch")
+        if g_action is None and g_logp is None:
+            raise ValueError("squashed_grad_torch: nothing to compute (g_action and g_logp are both None)")
+        if g_action is not None:
+            self._check_tensor("g_action", g_action, torch.float32, (n, 2))
+        if g_logp is not None:
+            self._check_tensor("g_logp", g_logp, torch.float32, (n,))
+        L = sp.n_hidden + 1
+        par = sp.tensors
+        if out is None:
+            out = dict(actor=[(torch.empty_like(par[2 * l]), torch.empty_like(par[2 * l + 1])) for l in range(L)])
+        g = _native.SgSquashedGrads(struct_size=C.sizeof(_native.SgSquashedGrads))
+        pairs = [tuple(x) for x in out["actor"]]
+        if len(pairs) != L:
+            raise ValueError(f"out['actor']: expected {L} (weight, bias) pairs, got {len(pairs)}")
+        for l, (w, b) in enumerate(pairs):
+            self._check_tensor(f"out['actor'][{l}] weight", w, torch.float32, tuple(par[2 * l].shape))
+            self._check_tensor(f"out['actor'][{l}] bias", b, torch.float32, tuple(par[2 * l + 1].shape))
+            g.actor.weight[l], g.actor.bias[l] = w.data_ptr(), b.data_ptr()
+        ws = self._grad_workspace(sp, int(self._lib.sg_squashed_grad_workspace_bytes(self._h, C.byref(sp.struct), n)), n, obs.device,
+                                  "squashed_grad_torch")
+        self._ck(self._lib.sg_squashed_grad_device(self._h, C.byref(sp.struct), n, _ptr(obs), _ptr(eps), _ptr(g_action), _ptr(g_logp), C.byref(g),
+                                                   _ptr(ws), ws.numel(), self._stream()), "sg_squashed_grad_device")
+        return out
+
+    def squashed_sample_torch(self, sp, obs, eps=None):
+        """action, logp = tanh(mean + exp(log_std) eps) and its log-prob (eps None: zeros), differentiable with respect to the actor's
+        tensors of the handle: ONE torch.autograd.Function over squashed_sample_raw_torch whose backward is one squashed_grad_torch
+        call (a None g for an output the loss did not use).  obs and eps get None.  The SAC actor loss stays on the device:
+            a, lp = env.squashed_sample_torch(sp, obs, torch.randn_like(...))
+            (alpha * lp - torch.min(*env.q_evaluate_torch(q, obs, a))).mean().backward()"""
+        self._squashed_rows(sp, obs, eps, "squashed_sample_torch")
+        return _squashed_sample_function().apply(self, sp, obs, eps, *sp.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

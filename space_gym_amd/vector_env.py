@@ -163,6 +163,23 @@ class SquashedPolicy:
         self.workspace = None  # squashed_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
+# per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id
+_NET_HANDLES = {Policy: ("policy", "policy_torch", "a = mean + exp(log_std) eps"), QNet: ("q", "q_torch", "the Q critics"),
+                SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor")}
+
+
+def _activation_code(activation):
+    if activation not in ("tanh", "relu"):
+        raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+    return 1 if activation == "relu" else 0
+
+
+def _empty_pairs(like):
+    """(weight, bias) gradient tensors for the parameters like = (w0, b0, w1, b1, ...)"""
+    import torch
+    return [(torch.empty_like(like[l]), torch.empty_like(like[l + 1])) for l in range(0, len(like), 2)]
+
+
 _POLICY_EVALUATE = None
 _Q_EVALUATE = None
 _POLICY_ACTION = None
@@ -1237,6 +1254,81 @@ class SpaceGymVectorEnv:
                                          ptr(out["returns"]), self._stream()), "sg_gae_device")
         return out["advantage"], out["returns"]
 
+    # ------------------------------------------------------------------ what the net handles and their methods share
+    def _mlp_layers(self, name, layers, fan_in, out, mlp, keep):
+        """checks one net [(weight, bias), ...] of fan_in -> hidden -> ... -> out, writes its pointers into the sg_policy_mlp `mlp`,
+        appends its tensors to `keep` and returns (n_hidden, hidden)"""
+        import torch
+        layers = [tuple(l) for l in layers]
+        n_hidden = len(layers) - 1
+        if not 1 <= n_hidden <= 3:
+            raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
+        w0 = layers[0][0]
+        if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
+            raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {fan_in})")
+        hidden = int(w0.shape[0])
+        if not 1 <= hidden <= 128:
+            raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
+        for l, (w, b) in enumerate(layers):
+            width = out if l == n_hidden else hidden
+            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
+            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
+            mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
+            keep.extend((w, b))
+            fan_in = hidden
+        return n_hidden, hidden
+
+    def _net_handle(self, handle, cls, who=None):
+        """checks a handle's class and, for `who` (a method of the continuous ids only), the id's action space"""
+        name, maker, subject = _NET_HANDLES[cls]
+        if not isinstance(handle, cls):
+            raise ValueError(f"{name}: expected the handle {maker} returns")
+        if who is not None and self.discrete:
+            raise ValueError(f"{who}: {subject} needs a continuous id; the discrete ids are not served")
+
+    def _net_rows(self, handle, cls, obs, who=None, **cols):
+        """checks (handle, obs [n, D]) as _net_handle and a column beside obs -- action=: [n, 2], int32 [n] under a discrete id's
+        Policy; eps=: [n, 2], or None -- and returns n"""
+        import torch
+        self._net_handle(handle, cls, who)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
+        if "action" in cols:
+            index = self.discrete and cls is Policy
+            self._check_tensor("action", cols["action"], torch.int32 if index else torch.float32, (n,) if index else (n, 2))
+        if cols.get("eps") is not None:
+            self._check_tensor("eps", cols["eps"], torch.float32, (n, 2))
+        return n
+
+    def _grad_pairs(self, name, pairs, like, mlp):
+        """checks the (weight, bias) gradient tensors of one net against its parameters `like` (w0, b0, w1, ...) and writes their
+        pointers into the sg_policy_grads_mlp `mlp`"""
+        import torch
+        pairs = [tuple(x) for x in pairs]
+        if 2 * len(pairs) != len(like):
+            raise ValueError(f"{name}: expected {len(like) // 2} (weight, bias) pairs, got {len(pairs)}")
+        for l, (w, b) in enumerate(pairs):
+            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, tuple(like[2 * l].shape))
+            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, tuple(like[2 * l + 1].shape))
+            mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
+
+    def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None):
+        """the workspace tensor cached on a Policy / QNet / SquashedPolicy handle, grown when n needs more -- never inside a capture;
+        refused: what the error names when the engine refuses the net or n (default: who)"""
+        import torch
+        need = int(getattr(self._lib, bytes_fn)(self._h, C.byref(handle.struct), n))
+        if need == 0:
+            self._ck(-1, refused or who)
+        ws = handle.workspace
+        if ws is None or ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError(f"{who}: the workspace ({0 if ws is None else ws.numel()} bytes) is too small for n = {n} ({need} bytes) "
+                                 "and cannot be allocated during a graph capture: make one warm-up call with this n before capturing")
+            ws = handle.workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
     # ------------------------------------------------------------------ actor-critic policy on the device, closed-loop rollouts
     def policy_torch(self, actor, critic=None, log_std=None, activation="tanh"):
         """A handle on a small MLP actor-critic whose parameters stay where they are (sg_policy: no copy, no transpose; what an
@@ -1246,36 +1338,12 @@ class SpaceGymVectorEnv:
         values).  Parameters of nn.Linear modules pass as they are: [(m.weight, m.bias) for m in linears].  activation: "tanh" or
         "relu", after every hidden layer."""
         import torch
-        if activation not in ("tanh", "relu"):
-            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
         head = 6 if self.discrete else 2
-        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=1 if activation == "relu" else 0, head=head)
+        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=_activation_code(activation), head=head)
         keep = []
-
-        def net(name, layers, out, mlp):
-            layers = [tuple(l) for l in layers]
-            n_hidden = len(layers) - 1
-            if not 1 <= n_hidden <= 3:
-                raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
-            w0 = layers[0][0]
-            if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
-                raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {self.obs_dim})")
-            hidden = int(w0.shape[0])
-            if not 1 <= hidden <= 128:
-                raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
-            fan_in = self.obs_dim
-            for l, (w, b) in enumerate(layers):
-                width = out if l == n_hidden else hidden
-                self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
-                self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
-                mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
-                keep.extend((w, b))
-                fan_in = hidden
-            return n_hidden, hidden
-
-        p.n_hidden, p.hidden = net("actor", actor, head, p.actor)
+        p.n_hidden, p.hidden = self._mlp_layers("actor", actor, self.obs_dim, head, p.actor, keep)
         if critic is not None:
-            if net("critic", critic, 1, p.critic) != (p.n_hidden, p.hidden):
+            if self._mlp_layers("critic", critic, self.obs_dim, 1, p.critic, keep) != (p.n_hidden, p.hidden):
                 raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
         if self.discrete:
             if log_std is not None:
@@ -1295,8 +1363,7 @@ class SpaceGymVectorEnv:
         Env i's noise is a function of (seed, step, env_index_base + i); deterministic: the mean / the first argmax.
         out: dict action / logp / value of tensors to fill (allocated when absent)."""
         import torch
-        if not isinstance(policy, Policy):
-            raise ValueError("policy: expected the handle policy_torch returns")
+        self._net_handle(policy, Policy)
         B, D = self.num_envs, self.obs_dim
         self._check_tensor("obs", obs, torch.float32, (B, D))
         if out is None:
@@ -1311,11 +1378,8 @@ class SpaceGymVectorEnv:
                     raise ValueError("out['value']: the policy has no critic")
                 self._check_tensor("out['value']", out["value"], torch.float32, (B,))
         value = out.get("value")
-        self._ck(self._lib.sg_policy_act_device(self._h, C.byref(policy.struct), C.c_void_p(obs.data_ptr()), int(seed), int(step),
-                                                int(bool(deterministic)), C.c_void_p(out["action"].data_ptr()),
-                                                C.c_void_p(out["logp"].data_ptr()),
-                                                C.c_void_p(value.data_ptr()) if value is not None else None, self._stream()),
-                 "sg_policy_act_device")
+        self._ck(self._lib.sg_policy_act_device(self._h, C.byref(policy.struct), _ptr(obs), int(seed), int(step), int(bool(deterministic)),
+                                                _ptr(out["action"]), _ptr(out["logp"]), _ptr(value), self._stream()), "sg_policy_act_device")
         return out["action"], out["logp"], value
 
     def _terminal_list_struct(self, terminal):
@@ -1345,8 +1409,7 @@ class SpaceGymVectorEnv:
             env.gae_torch(reward, done, trunc, value[:-1], value[-1], terminal=env.value_list_torch(terminal, terminal["value"]))
         needs nothing in between."""
         import torch
-        if not isinstance(policy, Policy):
-            raise ValueError("policy: expected the handle policy_torch returns")
+        self._net_handle(policy, Policy)
         if not isinstance(action, torch.Tensor) or action.dim() < 2 or int(action.shape[0]) < 1:
             raise ValueError("action: expected a CUDA tensor of at least one step")
         K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
@@ -1370,28 +1433,13 @@ class SpaceGymVectorEnv:
                     terminal["value"] = torch.empty(cap, dtype=torch.float32, device=terminal["obs"].device)
                 self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
                 tv = terminal["value"]
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
         self._ck(self._lib.sg_rollout_policy_device(self._h, K, C.byref(policy.struct), int(seed), int(first_step), int(bool(deterministic)),
-                                                    ptr(obs), ptr(action), ptr(logp), ptr(value), ptr(reward), ptr(done), ptr(trunc),
-                                                    C.byref(tl) if tl is not None else None, ptr(tv), self._stream()),
+                                                    _ptr(obs), _ptr(action), _ptr(logp), _ptr(value), _ptr(reward), _ptr(done), _ptr(trunc),
+                                                    C.byref(tl) if tl is not None else None, _ptr(tv), self._stream()),
                  "sg_rollout_policy_device")
         return obs, action, logp, value, reward, done, trunc
 
     # ------------------------------------------------------------------ the learner's half: evaluate given actions, parameter gradients
-    def _policy_rows(self, policy, obs, action):
-        """checks (policy, obs [n, D], action [n, 2] / int32 [n]) and returns n"""
-        import torch
-        if not isinstance(policy, Policy):
-            raise ValueError("policy: expected the handle policy_torch returns")
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
-            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
-        n = int(obs.shape[0])
-        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
-        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (n,) if self.discrete else (n, 2))
-        return n
-
     def policy_evaluate_raw_torch(self, policy, obs, action, out=None):
         """(logp, entropy, value) float32 [n] of the given rows -- obs float32 [n, D], action float32 [n, 2] as policy_act_torch stored
         it (discrete ids: int32 [n]) -- under a policy_torch handle: one launch on torch's current stream, no autograd
@@ -1399,7 +1447,7 @@ class SpaceGymVectorEnv:
         logp are policy_act_torch's bit for bit.  out: dict logp / entropy / value of tensors to fill (allocated when None; an entry
         that is absent or None is not computed).  value is None without a critic."""
         import torch
-        n = self._policy_rows(policy, obs, action)
+        n = self._net_rows(policy, Policy, obs, action=action)
         if out is None:
             out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in (("logp", "entropy", "value") if policy.has_critic else ("logp", "entropy"))}
         else:
@@ -1410,26 +1458,9 @@ class SpaceGymVectorEnv:
             for k in ("logp", "entropy", "value"):
                 if out.get(k) is not None:
                     self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_policy_evaluate_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(action), ptr(out.get("logp")),
-                                                     ptr(out.get("entropy")), ptr(out.get("value")), self._stream()), "sg_policy_evaluate_device")
+        self._ck(self._lib.sg_policy_evaluate_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("logp")),
+                                                     _ptr(out.get("entropy")), _ptr(out.get("value")), self._stream()), "sg_policy_evaluate_device")
         return out.get("logp"), out.get("entropy"), out.get("value")
-
-    def _policy_grad_workspace(self, policy, n, device):
-        """the workspace tensor cached on the handle, grown when n needs more -- never inside a capture"""
-        import torch
-        need = int(self._lib.sg_policy_grad_workspace_bytes(self._h, C.byref(policy.struct), n))
-        if need == 0:
-            self._ck(-1, "sg_policy_grad_workspace_bytes")
-        ws = policy.workspace
-        if ws is None or ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise ValueError(f"policy_grad_torch: the workspace ({0 if ws is None else ws.numel()} bytes) is too small for n = {n} ({need} bytes) "
-                                 "and cannot be allocated during a graph capture: make one warm-up call with this n before capturing")
-            ws = policy.workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
 
     def policy_grad_torch(self, policy, obs, action, g_logp=None, g_entropy=None, g_value=None, out=None):
         """Gradients of a loss with respect to the policy's parameters, given the loss's gradients g_logp / g_entropy / g_value
@@ -1439,7 +1470,7 @@ class SpaceGymVectorEnv:
         None without g_value) / log_std (None for the discrete ids), WRITTEN, not accumulated; out: such a dict of tensors to fill.
         Same inputs and same n: the same bits."""
         import torch
-        n = self._policy_rows(policy, obs, action)
+        n = self._net_rows(policy, Policy, obs, action=action)
         for name, g in (("g_logp", g_logp), ("g_entropy", g_entropy), ("g_value", g_value)):
             if g is not None:
                 self._check_tensor(name, g, torch.float32, (n,))
@@ -1449,25 +1480,14 @@ class SpaceGymVectorEnv:
         params = policy.tensors
         a_par, c_par = params[:2 * L], params[2 * L:4 * L] if policy.has_critic else ()
         if out is None:
-            pairs = lambda ts: [(torch.empty_like(ts[2 * l]), torch.empty_like(ts[2 * l + 1])) for l in range(L)]
-            out = dict(actor=pairs(a_par), critic=pairs(c_par) if g_value is not None else None,
+            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if g_value is not None else None,
                        log_std=None if self.discrete else torch.empty_like(params[-1]))
         g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
-
-        def fill(name, mlp, pairs, like):
-            pairs = [tuple(x) for x in pairs]
-            if len(pairs) != L:
-                raise ValueError(f"out['{name}']: expected {L} (weight, bias) pairs, got {len(pairs)}")
-            for l, (w, b) in enumerate(pairs):
-                self._check_tensor(f"out['{name}'][{l}] weight", w, torch.float32, tuple(like[2 * l].shape))
-                self._check_tensor(f"out['{name}'][{l}] bias", b, torch.float32, tuple(like[2 * l + 1].shape))
-                mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
-
-        fill("actor", g.actor, out["actor"], a_par)
+        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
         if out.get("critic") is not None:
             if not policy.has_critic:
                 raise ValueError("out['critic']: the policy has no critic")
-            fill("critic", g.critic, out["critic"], c_par)
+            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
         elif g_value is not None:
             raise ValueError("out['critic']: g_value is given; the critic's gradients need tensors")
         if self.discrete:
@@ -1478,12 +1498,9 @@ class SpaceGymVectorEnv:
                 raise ValueError("out['log_std']: expected a float32 [2] tensor")
             self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
             g.log_std = out["log_std"].data_ptr()
-        ws = self._policy_grad_workspace(policy, n, obs.device)
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_policy_grad_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(action), ptr(g_logp), ptr(g_entropy),
-                                                 ptr(g_value), C.byref(g), ptr(ws), ws.numel(), self._stream()), "sg_policy_grad_device")
+        ws = self._grad_workspace(policy, "sg_policy_grad_workspace_bytes", n, obs.device, "policy_grad_torch", "sg_policy_grad_workspace_bytes")
+        self._ck(self._lib.sg_policy_grad_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(action), _ptr(g_logp), _ptr(g_entropy),
+                                                 _ptr(g_value), C.byref(g), _ptr(ws), ws.numel(), self._stream()), "sg_policy_grad_device")
         return out
 
     def policy_evaluate_torch(self, policy, obs, action):
@@ -1492,7 +1509,7 @@ class SpaceGymVectorEnv:
         backward is policy_grad_torch (no [n, hidden] activation is kept between the two; obs and action get no gradient).  Write
         the loss in torch on the three [n] vectors and call backward(): the parameters' .grad accumulate as usual.  Under
         torch.no_grad(), or when no parameter requires grad, it is the plain forward.  value is None without a critic."""
-        self._policy_rows(policy, obs, action)
+        self._net_rows(policy, Policy, obs, action=action)
         return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
 
     # ------------------------------------------------------------------ the off-policy learner's nets: twin Q critics, action gradients
@@ -1501,60 +1518,26 @@ class SpaceGymVectorEnv:
         is a second handle).  critics: a list of one or two nets, each a list [(weight, bias), ...] of float32 CUDA tensors in
         torch.nn.Linear layout -- obs_dim + 2 -> hidden (1 .. 3 layers of one width 1 .. 128) -> 1, on the row [obs | action].
         Continuous ids only.  The action is used as given: nothing clamps it."""
-        import torch
         if self.discrete:
             raise ValueError("q_torch: the Q critics take the continuous ids' 2-vector action; the discrete ids are not served")
-        if activation not in ("tanh", "relu"):
-            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+        code = _activation_code(activation)
         critics = [list(c) for c in critics]
         if not 1 <= len(critics) <= 2:
             raise ValueError(f"critics: expected one or two nets, got {len(critics)}")
-        q = _native.SgQnet(struct_size=C.sizeof(_native.SgQnet), n_critics=len(critics), activation=1 if activation == "relu" else 0)
-        keep, shapes = [], []
-        for c, layers in enumerate(critics):
-            name = f"critics[{c}]"
-            layers = [tuple(l) for l in layers]
-            n_hidden = len(layers) - 1
-            if not 1 <= n_hidden <= 3:
-                raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
-            w0 = layers[0][0]
-            if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
-                raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {self.obs_dim + 2})")
-            hidden = int(w0.shape[0])
-            if not 1 <= hidden <= 128:
-                raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
-            fan_in = self.obs_dim + 2
-            for l, (w, b) in enumerate(layers):
-                width = 1 if l == n_hidden else hidden
-                self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
-                self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
-                q.critic[c].weight[l], q.critic[c].bias[l] = w.data_ptr(), b.data_ptr()
-                keep.extend((w, b))
-                fan_in = hidden
-            shapes.append((n_hidden, hidden))
+        q = _native.SgQnet(struct_size=C.sizeof(_native.SgQnet), n_critics=len(critics), activation=code)
+        keep = []
+        shapes = [self._mlp_layers(f"critics[{c}]", layers, self.obs_dim + 2, 1, q.critic[c], keep) for c, layers in enumerate(critics)]
         if len(set(shapes)) != 1:
             raise ValueError(f"critics[1]: expected {shapes[0][0]} hidden layers of width {shapes[0][1]}, like critics[0]")
         q.n_hidden, q.hidden = shapes[0]
         return QNet(q, keep)
-
-    def _q_rows(self, q, obs, action):
-        """checks (q, obs [n, D], action [n, 2]) and returns n"""
-        import torch
-        if not isinstance(q, QNet):
-            raise ValueError("q: expected the handle q_torch returns")
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
-            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
-        n = int(obs.shape[0])
-        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
-        self._check_tensor("action", action, torch.float32, (n, 2))
-        return n
 
     def q_evaluate_raw_torch(self, q, obs, action, out=None):
         """(q1, q2) float32 [n] of the rows obs float32 [n, D], action float32 [n, 2] under a q_torch handle; q2 is None with one
         critic.  One launch on torch's current stream, no host synchronisation, no autograd (sg_q_evaluate_device; graph-capturable).
         out: dict q1 / q2 of tensors to fill (allocated when None; an entry that is absent or None is not computed)."""
         import torch
-        n = self._q_rows(q, obs, action)
+        n = self._net_rows(q, QNet, obs, action=action)
         if out is None:
             out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in ("q1", "q2")[:q.n_critics]}
         else:
@@ -1565,25 +1548,9 @@ class SpaceGymVectorEnv:
             for k in ("q1", "q2"):
                 if out.get(k) is not None:
                     self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_q_evaluate_device(self._h, C.byref(q.struct), n, ptr(obs), ptr(action), ptr(out.get("q1")), ptr(out.get("q2")),
+        self._ck(self._lib.sg_q_evaluate_device(self._h, C.byref(q.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("q1")), _ptr(out.get("q2")),
                                                 self._stream()), "sg_q_evaluate_device")
         return out.get("q1"), out.get("q2")
-
-    def _grad_workspace(self, handle, need, n, device, who):
-        """the workspace tensor cached on a Policy / QNet / SquashedPolicy handle, grown when n needs more -- never inside a capture"""
-        import torch
-        if need == 0:
-            self._ck(-1, who)
-        ws = handle.workspace
-        if ws is None or ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise ValueError(f"{who}: the workspace ({0 if ws is None else ws.numel()} bytes) is too small for n = {n} ({need} bytes) "
-                                 "and cannot be allocated during a graph capture: make one warm-up call with this n before capturing")
-            ws = handle.workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
 
     def q_grad_torch(self, q, obs, action, g_q1=None, g_q2=None, params=True, action_grad=False, out=None):
         """The critics' half of a backward pass, given the loss's gradients g_q1 / g_q2 (float32 [n], None: zeros) by
@@ -1596,7 +1563,7 @@ class SpaceGymVectorEnv:
         out: such a dict of tensors to fill.  With params the call is graph-capturable after one warm-up call with the same n (which
         sizes the workspace kept on the handle).  Same inputs and same n: the same bits."""
         import torch
-        n = self._q_rows(q, obs, action)
+        n = self._net_rows(q, QNet, obs, action=action)
         for name, g in (("g_q1", g_q1), ("g_q2", g_q2)):
             if g is not None:
                 self._check_tensor(name, g, torch.float32, (n,))
@@ -1607,7 +1574,7 @@ class SpaceGymVectorEnv:
         L = q.n_hidden + 1
         like = [q.tensors[2 * L * c:2 * L * (c + 1)] for c in range(q.n_critics)]
         if out is None:
-            out = dict(critics=[[(torch.empty_like(ts[2 * l]), torch.empty_like(ts[2 * l + 1])) for l in range(L)] for ts in like] if params else None,
+            out = dict(critics=[_empty_pairs(ts) for ts in like] if params else None,
                        action=torch.empty((n, 2), dtype=torch.float32, device=obs.device) if action_grad else None)
         else:
             if params and out.get("critics") is None:
@@ -1622,22 +1589,13 @@ class SpaceGymVectorEnv:
             if len(nets) != q.n_critics:
                 raise ValueError(f"out['critics']: expected {q.n_critics} nets, got {len(nets)}")
             for c, pairs in enumerate(nets):
-                pairs = [tuple(x) for x in pairs]
-                if len(pairs) != L:
-                    raise ValueError(f"out['critics'][{c}]: expected {L} (weight, bias) pairs, got {len(pairs)}")
-                for l, (w, b) in enumerate(pairs):
-                    self._check_tensor(f"out['critics'][{c}][{l}] weight", w, torch.float32, tuple(like[c][2 * l].shape))
-                    self._check_tensor(f"out['critics'][{c}][{l}] bias", b, torch.float32, tuple(like[c][2 * l + 1].shape))
-                    g.critic[c].weight[l], g.critic[c].bias[l] = w.data_ptr(), b.data_ptr()
+                self._grad_pairs(f"out['critics'][{c}]", pairs, like[c], g.critic[c])
         if action_grad:
             self._check_tensor("out['action']", out["action"], torch.float32, (n, 2))
         if params:
-            ws = self._grad_workspace(q, int(self._lib.sg_q_grad_workspace_bytes(self._h, C.byref(q.struct), n)), n, obs.device, "q_grad_torch")
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_q_grad_device(self._h, C.byref(q.struct), n, ptr(obs), ptr(action), ptr(g_q1), ptr(g_q2),
-                                            C.byref(g) if g is not None else None, ptr(out["action"]), ptr(ws),
+            ws = self._grad_workspace(q, "sg_q_grad_workspace_bytes", n, obs.device, "q_grad_torch")
+        self._ck(self._lib.sg_q_grad_device(self._h, C.byref(q.struct), n, _ptr(obs), _ptr(action), _ptr(g_q1), _ptr(g_q2),
+                                            C.byref(g) if g is not None else None, _ptr(out["action"]), _ptr(ws),
                                             ws.numel() if ws is not None else 0, self._stream()), "sg_q_grad_device")
         return out
 
@@ -1647,37 +1605,20 @@ class SpaceGymVectorEnv:
         torch.autograd.Function whose forward is q_evaluate_raw_torch and whose backward is ONE q_grad_torch call -- params off when
         no parameter needs a gradient, action_grad only when the action needs one.  q2 is None with one critic.  With
         policy_action_torch it makes a TD3 / DDPG update plain torch on [n] vectors."""
-        self._q_rows(q, obs, action)
+        self._net_rows(q, QNet, obs, action=action)
         return _q_evaluate_function().apply(self, q, obs, action, *q.tensors)
-
-    def _policy_action_rows(self, policy, obs, eps, who):
-        import torch
-        if not isinstance(policy, Policy):
-            raise ValueError("policy: expected the handle policy_torch returns")
-        if self.discrete:
-            raise ValueError(f"{who}: a = mean + exp(log_std) eps needs a continuous id; the discrete ids are not served")
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
-            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
-        n = int(obs.shape[0])
-        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
-        if eps is not None:
-            self._check_tensor("eps", eps, torch.float32, (n, 2))
-        return n
 
     def policy_action_raw_torch(self, policy, obs, eps=None, out=None):
         """action float32 [n, 2] = mean(obs) + exp(log_std) * eps under a policy_torch handle of a continuous id, unclamped; eps
         float32 [n, 2] is the caller's noise, None: the mean (policy_act_torch(deterministic=True)'s action bit for bit).  One launch
         on torch's current stream, no autograd (sg_policy_action_device; graph-capturable).  out: the tensor to fill."""
         import torch
-        n = self._policy_action_rows(policy, obs, eps, "policy_action_raw_torch")
+        n = self._net_rows(policy, Policy, obs, "policy_action_raw_torch", eps=eps)
         if out is None:
             out = torch.empty((n, 2), dtype=torch.float32, device=obs.device)
         else:
             self._check_tensor("out", out, torch.float32, (n, 2))
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_policy_action_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(eps), ptr(out), self._stream()),
+        self._ck(self._lib.sg_policy_action_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(eps), _ptr(out), self._stream()),
                  "sg_policy_action_device")
         return out
 
@@ -1687,31 +1628,20 @@ class SpaceGymVectorEnv:
         two launches with another score and its workspace.  Returns dict actor (list of (weight, bias) gradients) / log_std, WRITTEN,
         not accumulated; the policy's critic is not involved.  out: such a dict of tensors to fill."""
         import torch
-        n = self._policy_action_rows(policy, obs, eps, "policy_action_grad_torch")
+        n = self._net_rows(policy, Policy, obs, "policy_action_grad_torch", eps=eps)
         self._check_tensor("g_action", g_action, torch.float32, (n, 2))
         L = policy.n_hidden + 1
         a_par = policy.tensors[:2 * L]
         if out is None:
-            out = dict(actor=[(torch.empty_like(a_par[2 * l]), torch.empty_like(a_par[2 * l + 1])) for l in range(L)],
-                       log_std=torch.empty_like(policy.tensors[-1]))
+            out = dict(actor=_empty_pairs(a_par), log_std=torch.empty_like(policy.tensors[-1]))
         g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
-        pairs = [tuple(x) for x in out["actor"]]
-        if len(pairs) != L:
-            raise ValueError(f"out['actor']: expected {L} (weight, bias) pairs, got {len(pairs)}")
-        for l, (w, b) in enumerate(pairs):
-            self._check_tensor(f"out['actor'][{l}] weight", w, torch.float32, tuple(a_par[2 * l].shape))
-            self._check_tensor(f"out['actor'][{l}] bias", b, torch.float32, tuple(a_par[2 * l + 1].shape))
-            g.actor.weight[l], g.actor.bias[l] = w.data_ptr(), b.data_ptr()
+        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
         if out.get("log_std") is None:
             raise ValueError("out['log_std']: expected a float32 [2] tensor")
         self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
         g.log_std = out["log_std"].data_ptr()
-        ws = self._grad_workspace(policy, int(self._lib.sg_policy_grad_workspace_bytes(self._h, C.byref(policy.struct), n)), n, obs.device,
-                                  "policy_action_grad_torch")
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        self._ck(self._lib.sg_policy_action_grad_device(self._h, C.byref(policy.struct), n, ptr(obs), ptr(eps), ptr(g_action), C.byref(g), ptr(ws),
+        ws = self._grad_workspace(policy, "sg_policy_grad_workspace_bytes", n, obs.device, "policy_action_grad_torch")
+        self._ck(self._lib.sg_policy_action_grad_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(eps), _ptr(g_action), C.byref(g), _ptr(ws),
                                                         ws.numel(), self._stream()), "sg_policy_action_grad_device")
         return out
 
@@ -1719,7 +1649,7 @@ class SpaceGymVectorEnv:
         """action = mean(obs) + exp(log_std) * eps (eps None: the mean), differentiable with respect to the actor's tensors and log_std
         of the handle: a torch.autograd.Function over policy_action_raw_torch / policy_action_grad_torch.  obs and eps get None.  The
         action is unclamped; clamp it in torch where the algorithm wants that."""
-        self._policy_action_rows(policy, obs, eps, "policy_action_torch")
+        self._net_rows(policy, Policy, obs, "policy_action_torch", eps=eps)
         return _policy_action_function().apply(self, policy, obs, eps, *policy.tensors)
 
     # ------------------------------------------------------------------ the SAC actor: tanh-squashed Gaussian, state-dependent log_std
@@ -1729,55 +1659,19 @@ class SpaceGymVectorEnv:
         1 .. 128) -> 4: head outputs 0, 1 are the mean, 2, 3 the raw log_std, clamped to log_std_bounds (SB3's -20, 2).  The action
         is tanh(mean + exp(log_std) eps) in [-1, 1]^2, logp the squashed Gaussian's.  Continuous ids only."""
         import math
-
-        import torch
         if self.discrete:
-            raise ValueError("squashed_policy_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
-        if activation not in ("tanh", "relu"):
-            raise ValueError(f"activation: expected 'tanh' or 'relu', got {activation!r}")
+            raise ValueError(f"squashed_policy_torch: {_NET_HANDLES[SquashedPolicy][2]} needs a continuous id; the discrete ids are not served")
+        code = _activation_code(activation)
         try:
             lo, hi = (float(x) for x in log_std_bounds)
         except (TypeError, ValueError):
             raise ValueError(f"log_std_bounds: expected (min, max), got {log_std_bounds!r}") from None
         if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
             raise ValueError(f"log_std_bounds: expected finite min <= max, got {log_std_bounds!r}")
-        p = _native.SgSquashedPolicy(struct_size=C.sizeof(_native.SgSquashedPolicy), activation=1 if activation == "relu" else 0,
-                                     log_std_min=lo, log_std_max=hi)
-        layers = [tuple(l) for l in actor]
-        n_hidden = len(layers) - 1
-        if not 1 <= n_hidden <= 3:
-            raise ValueError(f"actor: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
-        w0 = layers[0][0]
-        if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
-            raise ValueError(f"actor[0]: expected a weight of shape (hidden, {self.obs_dim})")
-        hidden = int(w0.shape[0])
-        if not 1 <= hidden <= 128:
-            raise ValueError(f"actor: hidden must be 1 .. 128, got {hidden}")
-        keep, fan_in = [], self.obs_dim
-        for l, (w, b) in enumerate(layers):
-            width = 4 if l == n_hidden else hidden
-            self._check_tensor(f"actor[{l}] weight", w, torch.float32, (width, fan_in))
-            self._check_tensor(f"actor[{l}] bias", b, torch.float32, (width,))
-            p.actor.weight[l], p.actor.bias[l] = w.data_ptr(), b.data_ptr()
-            keep.extend((w, b))
-            fan_in = hidden
-        p.n_hidden, p.hidden = n_hidden, hidden
+        p = _native.SgSquashedPolicy(struct_size=C.sizeof(_native.SgSquashedPolicy), activation=code, log_std_min=lo, log_std_max=hi)
+        keep = []
+        p.n_hidden, p.hidden = self._mlp_layers("actor", actor, self.obs_dim, 4, p.actor, keep)
         return SquashedPolicy(p, keep)
-
-    def _squashed_rows(self, sp, obs, eps, who):
-        """checks (sp, obs [n, D], eps [n, 2] or None) and returns n"""
-        import torch
-        if not isinstance(sp, SquashedPolicy):
-            raise ValueError("sp: expected the handle squashed_policy_torch returns")
-        if self.discrete:
-            raise ValueError(f"{who}: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
-            raise ValueError(f"obs: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
-        n = int(obs.shape[0])
-        self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
-        if eps is not None:
-            self._check_tensor("eps", eps, torch.float32, (n, 2))
-        return n
 
     def _squashed_out(self, out, n, device):
         import torch
@@ -1796,10 +1690,7 @@ class SpaceGymVectorEnv:
         function of (seed, step, env_index_base + i); deterministic: tanh(mean).  out: dict action / logp of tensors to fill (logp
         absent or None: not computed)."""
         import torch
-        if not isinstance(sp, SquashedPolicy):
-            raise ValueError("sp: expected the handle squashed_policy_torch returns")
-        if self.discrete:
-            raise ValueError("squashed_act_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        self._net_handle(sp, SquashedPolicy, "squashed_act_torch")
         B, D = self.num_envs, self.obs_dim
         self._check_tensor("obs", obs, torch.float32, (B, D))
         out = self._squashed_out(out, B, obs.device)
@@ -1814,10 +1705,7 @@ class SpaceGymVectorEnv:
         done, trunc uint8 [K, B]; logp float32 [K, B] or None.  terminal: a terminal_list_torch dict, filled like rollout_torch's.  The
         buffers may be a replay ring's rows(K)."""
         import torch
-        if not isinstance(sp, SquashedPolicy):
-            raise ValueError("sp: expected the handle squashed_policy_torch returns")
-        if self.discrete:
-            raise ValueError("rollout_squashed_torch: the squashed Gaussian actor needs a continuous id; the discrete ids are not served")
+        self._net_handle(sp, SquashedPolicy, "rollout_squashed_torch")
         if not isinstance(action, torch.Tensor) or action.dim() != 3 or int(action.shape[0]) < 1:
             raise ValueError("action: expected a CUDA tensor [K, B, 2] of at least one step")
         K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
@@ -1838,7 +1726,7 @@ class SpaceGymVectorEnv:
         """(action, logp) of the rows obs float32 [n, D] with the caller's noise eps float32 [n, 2] (None: zeros -- for the same rows
         squashed_act_torch(deterministic=True) bit for bit), any n >= 1: one launch on torch's current stream, no autograd
         (sg_squashed_sample_device; graph-capturable).  out: dict action / logp of tensors to fill (logp absent or None: not computed)."""
-        n = self._squashed_rows(sp, obs, eps, "squashed_sample_raw_torch")
+        n = self._net_rows(sp, SquashedPolicy, obs, "squashed_sample_raw_torch", eps=eps)
         out = self._squashed_out(out, n, obs.device)
         self._ck(self._lib.sg_squashed_sample_device(self._h, C.byref(sp.struct), n, _ptr(obs), _ptr(eps), _ptr(out["action"]), _ptr(out.get("logp")),
                                                      self._stream()), "sg_squashed_sample_device")
@@ -1851,27 +1739,18 @@ class SpaceGymVectorEnv:
         after one warm-up call with the same n (which sizes the workspace kept on the handle).  Returns dict actor: the list of
         (weight, bias) gradients, WRITTEN, not accumulated; out: such a dict of tensors to fill.  Same inputs and same n: the same bits."""
         import torch
-        n = self._squashed_rows(sp, obs, eps, "squashed_grad_torch")
+        n = self._net_rows(sp, SquashedPolicy, obs, "squashed_grad_torch", eps=eps)
         if g_action is None and g_logp is None:
             raise ValueError("squashed_grad_torch: nothing to compute (g_action and g_logp are both None)")
         if g_action is not None:
             self._check_tensor("g_action", g_action, torch.float32, (n, 2))
         if g_logp is not None:
             self._check_tensor("g_logp", g_logp, torch.float32, (n,))
-        L = sp.n_hidden + 1
-        par = sp.tensors
         if out is None:
-            out = dict(actor=[(torch.empty_like(par[2 * l]), torch.empty_like(par[2 * l + 1])) for l in range(L)])
+            out = dict(actor=_empty_pairs(sp.tensors))
         g = _native.SgSquashedGrads(struct_size=C.sizeof(_native.SgSquashedGrads))
-        pairs = [tuple(x) for x in out["actor"]]
-        if len(pairs) != L:
-            raise ValueError(f"out['actor']: expected {L} (weight, bias) pairs, got {len(pairs)}")
-        for l, (w, b) in enumerate(pairs):
-            self._check_tensor(f"out['actor'][{l}] weight", w, torch.float32, tuple(par[2 * l].shape))
-            self._check_tensor(f"out['actor'][{l}] bias", b, torch.float32, tuple(par[2 * l + 1].shape))
-            g.actor.weight[l], g.actor.bias[l] = w.data_ptr(), b.data_ptr()
-        ws = self._grad_workspace(sp, int(self._lib.sg_squashed_grad_workspace_bytes(self._h, C.byref(sp.struct), n)), n, obs.device,
-                                  "squashed_grad_torch")
+        self._grad_pairs("out['actor']", out["actor"], sp.tensors, g.actor)
+        ws = self._grad_workspace(sp, "sg_squashed_grad_workspace_bytes", n, obs.device, "squashed_grad_torch")
         self._ck(self._lib.sg_squashed_grad_device(self._h, C.byref(sp.struct), n, _ptr(obs), _ptr(eps), _ptr(g_action), _ptr(g_logp), C.byref(g),
                                                    _ptr(ws), ws.numel(), self._stream()), "sg_squashed_grad_device")
         return out
@@ -1882,7 +1761,7 @@ class SpaceGymVectorEnv:
         call (a None g for an output the loss did not use).  obs and eps get None.  The SAC actor loss stays on the device:
             a, lp = env.squashed_sample_torch(sp, obs, torch.randn_like(...))
             (alpha * lp - torch.min(*env.q_evaluate_torch(q, obs, a))).mean().backward()"""
-        self._squashed_rows(sp, obs, eps, "squashed_sample_torch")
+        self._net_rows(sp, SquashedPolicy, obs, "squashed_sample_torch", eps=eps)
         return _squashed_sample_function().apply(self, sp, obs, eps, *sp.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,

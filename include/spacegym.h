@@ -979,6 +979,80 @@ int sg_rollout_squashed_device(sg_env *env, int32_t n_steps, const sg_squashed_p
                                int32_t deterministic, float *obs, float *action, float *logp, float *reward, uint8_t *done,
                                uint8_t *truncated, const sg_terminal_list *terminal_list, void *hip_stream);
 
+/* The DQN head: one MLP Q(obs) -> 6 on the discrete ids (GoalDiscrete{2,3,4}-v0, KeplerDiscrete-v0), epsilon-greedy acting, the Q values
+ * a TD target and a TD loss need, and the gradients of a loss on them by the net's parameters -- DQN / Double DQN, with a per-env epsilon
+ * as Ape-X runs it on a wide vector env.  Discrete ids only (a continuous id is refused with a message).  The reference has no counterpart.
+ *   net   obs_dim -> hidden (x n_hidden) -> 6       head output j: Q(obs, action j)
+ * Every hidden layer is followed by the activation; the head is linear.  Parameters are float32 DEVICE pointers in torch.nn.Linear
+ * layout (the head is [6, hidden]), owned by the caller and read in place at every call, like sg_policy's; a target network is simply
+ * a second sg_dqn.  Arithmetic: sg_policy's -- float32 throughout, output neuron j starts at b[j] and takes fmaf(W[j][k], h[k], .) for
+ * k = 0, 1, ..., one row per lane, no atomics: a row's six Q values depend on that row and the parameters only.  "argmax" is always the
+ * FIRST j whose Q_j is the largest (a NaN Q_0 gives 0).  Every call takes the stream, allocates nothing, never synchronises and is
+ * hipGraph-capturable.  tests/dqn_model.py states all of it in NumPy; DESIGN section 22 has the kernels and the tolerances. */
+typedef struct sg_dqn {
+    uint32_t struct_size;  /* sizeof(sg_dqn) */
+    int32_t n_hidden;      /* hidden layers, 1 .. 3 */
+    int32_t hidden;        /* their width, 1 .. 128 */
+    int32_t activation;    /* SG_POLICY_TANH / SG_POLICY_RELU */
+    int32_t reserved;      /* 0 */
+    sg_policy_mlp net;     /* the head is [6, hidden] */
+} sg_dqn;
+/* Epsilon-greedy actions of the observation rows obs_dev float32 [num_envs, obs_dim] in ONE launch: action_out int32 [num_envs];
+ * q_out float32 [num_envs], may be NULL: the Q value of the action TAKEN.  Env i draws one Philox block o, key = seed, counter =
+ * (env_index_base + i, step lo, step hi, 7) -- stream tag 7, after the squashed actor's 6 -- and
+ *   explores iff u23(o0) < eps_i, u23(w) = ((w >> 9) + 0.5) / 2^23;  its action is then floor(o1 * 6 / 2^32), uniform on 0 .. 5 in exact
+ *   integer arithmetic;  otherwise it takes the argmax.
+ * eps_i is epsilon_dev[i] when epsilon_dev (float32 [num_envs], DEVICE memory) is given, else the host scalar epsilon: a captured graph
+ * anneals epsilon by writing that tensor, and every env may have its own (Ape-X).  With epsilon_dev NULL and epsilon == 0 nothing is
+ * drawn.  The values of epsilon_dev are not checked: <= 0 (or NaN) never explores, >= 1 always does, by the comparison.  Env i's
+ * results depend on its row, the parameters, eps_i and (seed, step, env_index_base + i) only.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a continuous id; a null dqn or a wrong struct_size or reserved; n_hidden
+ * outside 1 .. 3, hidden outside 1 .. 128, an unknown activation; a null weight or bias among the layers in use; a null obs_dev or
+ * action_out; an epsilon that is NaN or outside [0, 1] (checked with epsilon_dev given as well). */
+int sg_dqn_act_device(sg_env *env, const sg_dqn *dqn, const float *obs_dev, uint64_t seed, uint64_t step, float epsilon,
+                      const float *epsilon_dev, int32_t *action_out, float *q_out, void *hip_stream);
+/* n_steps closed-loop steps without a host synchronisation: sg_rollout_squashed_device's loop with sg_dqn_act_device.  obs float32
+ * [n_steps + 1, num_envs, obs_dim] with the current observations in row 0; action int32 [n_steps, num_envs]; q (may be NULL), reward,
+ * done, truncated [n_steps, num_envs].  For every t the call enqueues the act kernel with step = first_step + t (epsilon_dev is read by
+ * every one of them), then the single step sg_step_device enqueues, then the terminal list's records (terminal_list may be NULL;
+ * filled as by sg_rollout_policy_device): every output is bit for bit what that hand-written loop gives, with normalization on as
+ * well.  The buffers may be a replay ring's rows.
+ * Refused as sg_dqn_act_device refuses, and: n_steps < 1, a null obs, action, reward, done or truncated, an incomplete list. */
+int sg_rollout_dqn_device(sg_env *env, int32_t n_steps, const sg_dqn *dqn, uint64_t seed, uint64_t first_step, float epsilon,
+                          const float *epsilon_dev, float *obs, int32_t *action, float *q, float *reward, uint8_t *done,
+                          uint8_t *truncated, const sg_terminal_list *terminal_list, void *hip_stream);
+/* The Q values of the rows obs float32 [n, obs_dim], any n >= 1, in ONE launch:
+ *   q_all_out    float32 [n, 6]
+ *   q_taken_out  float32 [n] = Q[i][action[i]], action int32 [n], 0 .. 5 (any other value is the caller's error -- the kernels select by
+ *                comparison and never index with it, so it cannot reach out of bounds)
+ *   q_max_out    float32 [n] = max_j Q[i][j];  argmax_out int32 [n], the first argmax
+ * Each output may be NULL, not all four; action may be NULL when q_taken_out is.  q_taken, q_max and argmax are elements of q_all, bit
+ * for bit, and for the rows sg_dqn_act_device saw q_all / argmax are that kernel's bits (one device function serves both).  Plain DQN's
+ * target is q_max_out of the target net; Double DQN's is two calls: argmax_out of the online net on next_obs, then q_taken_out of the
+ * target net with it as action.
+ * Refused: whatever sg_dqn_act_device refuses of the dqn; n < 1; a null obs; no output; q_taken_out with a null action. */
+int sg_dqn_evaluate_device(sg_env *env, const sg_dqn *dqn, int64_t n, const float *obs, const int32_t *action, float *q_all_out,
+                           float *q_taken_out, float *q_max_out, int32_t *argmax_out, void *hip_stream);
+typedef struct sg_dqn_grads {
+    uint32_t struct_size;  /* sizeof(sg_dqn_grads) */
+    uint32_t reserved;     /* 0 */
+    sg_policy_grads_mlp net;
+} sg_dqn_grads;
+/* grads->net receives sum_i sum_j dz_ij d Q_j[i] / d theta for every weight and bias, dz_ij = g_all[i][j] + [j == action[i]] g_taken[i]:
+ * WRITTEN, not accumulated.  g_taken float32 [n] and g_all float32 [n, 6] are the loss's gradients by sg_dqn_evaluate_device's q_taken_out
+ * and q_all_out at the same (obs, action); each may be NULL (zeros), not both; action is needed when g_taken is given and not looked at
+ * otherwise.  g_all serves losses on all six values (a CQL logsumexp term, discrete SAC / soft Q) without another kernel.
+ * tanh' = 1 - h^2 of the activation h; relu' = [pre-activation > 0]: 0 at 0, as torch.  The forward pass is recomputed inside the
+ * launch.  Two launches, exactly sg_policy_grad_device's scheme: the backward, whose workgroups leave partial sums in `workspace` (at
+ * least sg_dqn_grad_workspace_bytes(env, dqn, n) bytes of device memory, any content), and a reduction of the partials in workgroup
+ * order; no atomics, a fixed summation order that is a function of n: the same inputs and the same n give the same bits.
+ * Refused: whatever sg_dqn_evaluate_device refuses of the dqn and the rows; both g NULL; g_taken with a null action; a null grads, a wrong
+ * struct_size or reserved; a null pointer among the net's gradient slots in use; a null workspace or one smaller than the query's answer. */
+int sg_dqn_grad_device(sg_env *env, const sg_dqn *dqn, int64_t n, const float *obs, const int32_t *action, const float *g_taken,
+                       const float *g_all, const sg_dqn_grads *grads, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_dqn_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid dqn or n */
+size_t sg_dqn_grad_workspace_bytes(sg_env *env, const sg_dqn *dqn, int64_t n);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

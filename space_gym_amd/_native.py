@@ -139,6 +139,17 @@ class SgSquashedGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("actor", SgPolicyMlp)]
 
 
+class SgDqn(C.Structure):
+    """sg_dqn (include/spacegym.h): the DQN head of the discrete ids -- one MLP Q(obs) -> 6, parameters read where the learner keeps them"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_hidden", C.c_int32), ("hidden", C.c_int32), ("activation", C.c_int32),
+                ("reserved", C.c_int32), ("net", SgPolicyMlp)]
+
+
+class SgDqnGrads(C.Structure):
+    """sg_dqn_grads (include/spacegym.h): where sg_dqn_grad_device writes the gradient of every parameter of an sg_dqn"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("net", SgPolicyMlp)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -240,6 +251,12 @@ SYMBOLS = {
     "sg_squashed_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgSquashedPolicy), C.c_int64]),
     "sg_rollout_squashed_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgSquashedPolicy), C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
                                              _vp, _vp, C.POINTER(SgTerminalList), _vp]),
+    "sg_dqn_act_device": (C.c_int, [_vp, C.POINTER(SgDqn), _vp, C.c_uint64, C.c_uint64, C.c_float, _vp, _vp, _vp, _vp]),
+    "sg_rollout_dqn_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgDqn), C.c_uint64, C.c_uint64, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        C.POINTER(SgTerminalList), _vp]),
+    "sg_dqn_evaluate_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_dqn_grad_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgDqnGrads), _vp, C.c_size_t, _vp]),
+    "sg_dqn_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgDqn), C.c_int64]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

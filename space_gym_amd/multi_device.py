@@ -144,6 +144,8 @@ class MultiDeviceVectorEnv:
     policy_action_torch = policy_action_raw_torch = policy_action_grad_torch = _no_policy
     squashed_policy_torch = squashed_act_torch = rollout_squashed_torch = _no_policy
     squashed_sample_torch = squashed_sample_raw_torch = squashed_grad_torch = _no_policy
+    dqn_torch = dqn_act_torch = rollout_dqn_torch = _no_policy
+    dqn_evaluate_torch = dqn_evaluate_raw_torch = dqn_grad_torch = _no_policy
 
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)

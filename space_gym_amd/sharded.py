@@ -144,6 +144,8 @@ class ShardedVectorEnv:
     policy_action_torch = policy_action_raw_torch = policy_action_grad_torch = _no_policy
     squashed_policy_torch = squashed_act_torch = rollout_squashed_torch = _no_policy
     squashed_sample_torch = squashed_sample_raw_torch = squashed_grad_torch = _no_policy
+    dqn_torch = dqn_act_torch = rollout_dqn_torch = _no_policy
+    dqn_evaluate_torch = dqn_evaluate_raw_torch = dqn_grad_torch = _no_policy
 
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""

@@ -163,9 +163,20 @@ class SquashedPolicy:
         self.workspace = None  # squashed_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
-# per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id
+class Dqn:
+    """What dqn_torch returns: the sg_dqn struct (include/spacegym.h) over the caller's parameter tensors, which it keeps alive;
+    n_hidden, hidden and activation describe the net.  A target network is a second handle."""
+
+    def __init__(self, struct, tensors):
+        self.struct, self.tensors = struct, tuple(tensors)
+        self.n_hidden, self.hidden = int(struct.n_hidden), int(struct.hidden)
+        self.activation = "relu" if struct.activation else "tanh"
+        self.workspace = None  # dqn_grad_torch's partial sums: a uint8 tensor, grown on demand
+
+
+# per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id (Dqn: a continuous one)
 _NET_HANDLES = {Policy: ("policy", "policy_torch", "a = mean + exp(log_std) eps"), QNet: ("q", "q_torch", "the Q critics"),
-                SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor")}
+                SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor"), Dqn: ("dqn", "dqn_torch", "the DQN head Q(obs) -> 6")}
 
 
 def _activation_code(activation):
@@ -184,6 +195,43 @@ _POLICY_EVALUATE = None
 _Q_EVALUATE = None
 _POLICY_ACTION = None
 _SQUASHED_SAMPLE = None
+_DQN_EVALUATE = None
+
+
+def _dqn_evaluate_function():
+    """the torch.autograd.Function behind dqn_evaluate_torch"""
+    global _DQN_EVALUATE
+    if _DQN_EVALUATE is not None:
+        return _DQN_EVALUATE
+    import torch
+
+    class DqnEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, dqn, obs, action, *params):
+            ctx.env, ctx.dqn, ctx.has_action = env, dqn, action is not None
+            ctx.save_for_backward(*((obs, action) if action is not None else (obs,)))
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
+            n = int(obs.shape[0])
+            out = dict(q_all=torch.empty((n, 6), dtype=torch.float32, device=obs.device))
+            if action is not None:
+                out["q_taken"] = torch.empty(n, dtype=torch.float32, device=obs.device)
+            q_all, q_taken = env.dqn_evaluate_raw_torch(dqn, obs, action, out=out)[:2]
+            return q_all if action is None else (q_all, q_taken)
+
+        @staticmethod
+        def backward(ctx, g_all, g_taken=None):
+            env, dqn = ctx.env, ctx.dqn
+            none = (None,) * (4 + len(dqn.tensors))
+            if (g_all is None and g_taken is None) or not any(ctx.needs_input_grad[4:]):
+                return none
+            obs = ctx.saved_tensors[0]
+            action = ctx.saved_tensors[1] if ctx.has_action and g_taken is not None else None
+            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            out = env.dqn_grad_torch(dqn, obs, action, con(g_taken), con(g_all))
+            return (None, None, None, None, *[t for pair in out["net"] for t in pair])
+
+    _DQN_EVALUATE = DqnEvaluate
+    return DqnEvaluate
 
 
 def _squashed_sample_function():
@@ -1288,7 +1336,7 @@ class SpaceGymVectorEnv:
 
     def _net_rows(self, handle, cls, obs, who=None, **cols):
         """checks (handle, obs [n, D]) as _net_handle and a column beside obs -- action=: [n, 2], int32 [n] under a discrete id's
-        Policy; eps=: [n, 2], or None -- and returns n"""
+        Policy or Dqn; eps=: [n, 2], or None -- and returns n"""
         import torch
         self._net_handle(handle, cls, who)
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
@@ -1296,7 +1344,7 @@ class SpaceGymVectorEnv:
         n = int(obs.shape[0])
         self._check_tensor("obs", obs, torch.float32, (n, self.obs_dim))
         if "action" in cols:
-            index = self.discrete and cls is Policy
+            index = self.discrete and cls in (Policy, Dqn)
             self._check_tensor("action", cols["action"], torch.int32 if index else torch.float32, (n,) if index else (n, 2))
         if cols.get("eps") is not None:
             self._check_tensor("eps", cols["eps"], torch.float32, (n, 2))
@@ -1315,7 +1363,7 @@ class SpaceGymVectorEnv:
             mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
 
     def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None):
-        """the workspace tensor cached on a Policy / QNet / SquashedPolicy handle, grown when n needs more -- never inside a capture;
+        """the workspace tensor cached on a Policy / QNet / SquashedPolicy / Dqn handle, grown when n needs more -- never inside a capture;
         refused: what the error names when the engine refuses the net or n (default: who)"""
         import torch
         need = int(getattr(self._lib, bytes_fn)(self._h, C.byref(handle.struct), n))
@@ -1519,7 +1567,8 @@ class SpaceGymVectorEnv:
         torch.nn.Linear layout -- obs_dim + 2 -> hidden (1 .. 3 layers of one width 1 .. 128) -> 1, on the row [obs | action].
         Continuous ids only.  The action is used as given: nothing clamps it."""
         if self.discrete:
-            raise ValueError("q_torch: the Q critics take the continuous ids' 2-vector action; the discrete ids are not served")
+            raise ValueError("q_torch: the Q critics take the continuous ids' 2-vector action; the discrete ids are not served "
+                             "(their Q head is dqn_torch's Q(obs) -> 6)")
         code = _activation_code(activation)
         critics = [list(c) for c in critics]
         if not 1 <= len(critics) <= 2:
@@ -1763,6 +1812,158 @@ class SpaceGymVectorEnv:
             (alpha * lp - torch.min(*env.q_evaluate_torch(q, obs, a))).mean().backward()"""
         self._net_rows(sp, SquashedPolicy, obs, "squashed_sample_torch", eps=eps)
         return _squashed_sample_function().apply(self, sp, obs, eps, *sp.tensors)
+
+    # ------------------------------------------------------------------ the DQN head of the discrete ids: Q(obs) -> 6, epsilon-greedy
+    def _dqn_handle(self, dqn, who):
+        """checks a dqn_torch handle and that the id is a discrete one"""
+        self._net_handle(dqn, Dqn)
+        if not self.discrete:
+            raise ValueError(f"{who}: {_NET_HANDLES[Dqn][2]} needs a discrete id; the continuous ids are not served")
+
+    def _dqn_rows(self, dqn, who, obs, action=None):
+        """_dqn_handle, obs [n, D] and (given) action int32 [n]; returns n"""
+        self._dqn_handle(dqn, who)
+        return self._net_rows(dqn, Dqn, obs, **({} if action is None else dict(action=action)))
+
+    def _dqn_epsilon(self, epsilon):
+        """(the host scalar, the per-env tensor or None) of an epsilon that is a float in [0, 1] or a float32 CUDA tensor [num_envs]"""
+        import math
+        import torch
+        if isinstance(epsilon, torch.Tensor):
+            self._check_tensor("epsilon", epsilon, torch.float32, (self.num_envs,))
+            return 0.0, epsilon
+        try:
+            eps = float(epsilon)
+        except (TypeError, ValueError):
+            raise ValueError(f"epsilon: expected a float in [0, 1] or a float32 CUDA tensor [num_envs], got {epsilon!r}") from None
+        if math.isnan(eps) or not 0.0 <= eps <= 1.0:
+            raise ValueError(f"epsilon: expected a float in [0, 1] or a float32 CUDA tensor [num_envs], got {epsilon!r}")
+        return eps, None
+
+    def dqn_torch(self, net, activation="relu"):
+        """A handle on a DQN head whose parameters stay where they are (sg_dqn: no copy, no transpose; a target network is a second
+        handle).  net: a list [(weight, bias), ...] of float32 CUDA tensors in torch.nn.Linear layout -- obs_dim -> hidden (1 .. 3
+        layers of one width 1 .. 128) -> 6: output j is Q(obs, action j).  Discrete ids only."""
+        if not self.discrete:
+            raise ValueError(f"dqn_torch: {_NET_HANDLES[Dqn][2]} needs a discrete id; the continuous ids are not served")
+        d = _native.SgDqn(struct_size=C.sizeof(_native.SgDqn), activation=_activation_code(activation))
+        keep = []
+        d.n_hidden, d.hidden = self._mlp_layers("net", net, self.obs_dim, 6, d.net, keep)
+        return Dqn(d, keep)
+
+    def dqn_act_torch(self, dqn, obs, seed=0, step=0, epsilon=0.0, out=None):
+        """(action, q) of the observations obs float32 [B, D] under a dqn_torch handle, epsilon-greedy, in one launch on torch's
+        current stream (sg_dqn_act_device; graph-capturable).  action int32 [B]; q float32 [B], the Q value of the action taken.
+        epsilon: a float in [0, 1], or a float32 CUDA tensor [B] of per-env values that is read on the device at every launch (a
+        captured graph anneals it by writing the tensor; its values are not checked: <= 0 never explores, >= 1 always does).  Env
+        i's draw is a function of (seed, step, env_index_base + i); epsilon 0.0: the first argmax, nothing drawn.  out: dict action /
+        q of tensors to fill (q absent or None: not computed)."""
+        import torch
+        self._dqn_handle(dqn, "dqn_act_torch")
+        B, D = self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (B, D))
+        eps, eps_dev = self._dqn_epsilon(epsilon)
+        if out is None:
+            out = dict(action=torch.empty(B, dtype=torch.int32, device=obs.device), q=torch.empty(B, dtype=torch.float32, device=obs.device))
+        else:
+            if out.get("action") is None:
+                raise ValueError("out['action']: expected an int32 [num_envs] tensor")
+            self._check_tensor("out['action']", out["action"], torch.int32, (B,))
+            if out.get("q") is not None:
+                self._check_tensor("out['q']", out["q"], torch.float32, (B,))
+        self._ck(self._lib.sg_dqn_act_device(self._h, C.byref(dqn.struct), _ptr(obs), int(seed), int(step), eps, _ptr(eps_dev),
+                                             _ptr(out["action"]), _ptr(out.get("q")), self._stream()), "sg_dqn_act_device")
+        return out["action"], out.get("q")
+
+    def rollout_dqn_torch(self, dqn, obs, action, reward, done, trunc, q=None, seed=0, first_step=0, epsilon=0.0, terminal=None):
+        """K closed-loop steps on torch's current stream without a host synchronisation (sg_rollout_dqn_device): for every t the net
+        acts on obs[t] (draw step first_step + t, epsilon as dqn_act_torch's) and the env steps into obs[t + 1], exactly as
+        dqn_act_torch followed by step_torch would.  obs float32 [K + 1, B, D] with the current observations in row 0; action int32
+        [K, B]; reward float32 / done, trunc uint8 [K, B]; q float32 [K, B] or None.  terminal: a terminal_list_torch dict, filled
+        like rollout_torch's.  The buffers may be a replay ring's rows(K)."""
+        import torch
+        self._dqn_handle(dqn, "rollout_dqn_torch")
+        if not isinstance(action, torch.Tensor) or action.dim() != 2 or int(action.shape[0]) < 1:
+            raise ValueError("action: expected a CUDA tensor [K, B] of at least one step")
+        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
+        self._check_tensor("action", action, torch.int32, (K, B))
+        if q is not None:
+            self._check_tensor("q", q, torch.float32, (K, B))
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        eps, eps_dev = self._dqn_epsilon(epsilon)
+        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
+        self._ck(self._lib.sg_rollout_dqn_device(self._h, K, C.byref(dqn.struct), int(seed), int(first_step), eps, _ptr(eps_dev), _ptr(obs),
+                                                 _ptr(action), _ptr(q), _ptr(reward), _ptr(done), _ptr(trunc),
+                                                 C.byref(tl) if tl is not None else None, self._stream()), "sg_rollout_dqn_device")
+        return obs, action, q, reward, done, trunc
+
+    def dqn_evaluate_raw_torch(self, dqn, obs, action=None, out=None):
+        """(q_all, q_taken, q_max, argmax) of the rows obs float32 [n, D], any n >= 1, under a dqn_torch handle: one launch on torch's
+        current stream, no autograd (sg_dqn_evaluate_device; graph-capturable).  q_all float32 [n, 6]; q_taken float32 [n] =
+        q_all[i, action[i]] for action int32 [n] (None without an action); q_max float32 [n]; argmax int32 [n], the first argmax --
+        all three elements of q_all bit for bit, and for the rows dqn_act_torch saw its bits.  out: dict q_all / q_taken / q_max /
+        argmax of tensors to fill (allocated when None; an entry that is absent or None is not computed).  Double DQN's target:
+        argmax of the online handle on next_obs, then q_taken of the target handle with it."""
+        import torch
+        n = self._dqn_rows(dqn, "dqn_evaluate_raw_torch", obs, action)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=obs.device)
+        if out is None:
+            out = dict(q_all=f32(n, 6), q_taken=f32(n) if action is not None else None, q_max=f32(n),
+                       argmax=torch.empty(n, dtype=torch.int32, device=obs.device))
+        else:
+            if all(out.get(k) is None for k in ("q_all", "q_taken", "q_max", "argmax")):
+                raise ValueError("out: expected at least one of q_all, q_taken, q_max, argmax")
+            if out.get("q_taken") is not None and action is None:
+                raise ValueError("action: out['q_taken'] is given; expected the int32 [n] actions")
+            for k, dtype, shape in (("q_all", torch.float32, (n, 6)), ("q_taken", torch.float32, (n,)), ("q_max", torch.float32, (n,)),
+                                    ("argmax", torch.int32, (n,))):
+                if out.get(k) is not None:
+                    self._check_tensor(f"out['{k}']", out[k], dtype, shape)
+        self._ck(self._lib.sg_dqn_evaluate_device(self._h, C.byref(dqn.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("q_all")),
+                                                  _ptr(out.get("q_taken")), _ptr(out.get("q_max")), _ptr(out.get("argmax")), self._stream()),
+                 "sg_dqn_evaluate_device")
+        return out.get("q_all"), out.get("q_taken"), out.get("q_max"), out.get("argmax")
+
+    def dqn_grad_torch(self, dqn, obs, action=None, g_taken=None, g_all=None, out=None):
+        """Gradients of a loss with respect to the net's parameters, given the loss's gradients g_taken float32 [n] and g_all float32
+        [n, 6] by dqn_evaluate_raw_torch's q_taken and q_all at the same (obs, action) (each may be None: zeros, not both; action
+        int32 [n] is needed with g_taken): sg_dqn_grad_device, two launches on torch's current stream, the forward pass recomputed
+        inside, graph-capturable after one warm-up call with the same n (which sizes the workspace kept on the handle).  Returns dict
+        net: the list of (weight, bias) gradients, WRITTEN, not accumulated; out: such a dict of tensors to fill.  Same inputs and
+        same n: the same bits."""
+        import torch
+        n = self._dqn_rows(dqn, "dqn_grad_torch", obs, action)
+        if g_taken is None and g_all is None:
+            raise ValueError("dqn_grad_torch: nothing to compute (g_taken and g_all are both None)")
+        if g_taken is not None:
+            if action is None:
+                raise ValueError("action: g_taken is given; expected the int32 [n] actions")
+            self._check_tensor("g_taken", g_taken, torch.float32, (n,))
+        if g_all is not None:
+            self._check_tensor("g_all", g_all, torch.float32, (n, 6))
+        if out is None:
+            out = dict(net=_empty_pairs(dqn.tensors))
+        g = _native.SgDqnGrads(struct_size=C.sizeof(_native.SgDqnGrads))
+        self._grad_pairs("out['net']", out["net"], dqn.tensors, g.net)
+        ws = self._grad_workspace(dqn, "sg_dqn_grad_workspace_bytes", n, obs.device, "dqn_grad_torch")
+        self._ck(self._lib.sg_dqn_grad_device(self._h, C.byref(dqn.struct), n, _ptr(obs), _ptr(action), _ptr(g_taken), _ptr(g_all), C.byref(g),
+                                              _ptr(ws), ws.numel(), self._stream()), "sg_dqn_grad_device")
+        return out
+
+    def dqn_evaluate_torch(self, dqn, obs, action=None):
+        """q_all, or (q_all, q_taken) with an action int32 [n]: the Q values of the rows under the CURRENT parameters, differentiable
+        with respect to the parameter tensors the handle holds: ONE torch.autograd.Function over dqn_evaluate_raw_torch whose backward
+        is one dqn_grad_torch call (a None g for an output the loss did not use).  obs and action get None.  q_max and argmax come
+        from the raw form; targets are computed under torch.no_grad().  A Double DQN update stays on the device:
+            with torch.no_grad():
+                a2 = env.dqn_evaluate_raw_torch(online, next_obs)[3]
+                target = reward + discount * env.dqn_evaluate_raw_torch(target_net, next_obs, a2)[1]
+            huber(env.dqn_evaluate_torch(online, obs, action)[1], target).mean().backward()"""
+        self._dqn_rows(dqn, "dqn_evaluate_torch", obs, action)
+        return _dqn_evaluate_function().apply(self, dqn, obs, action, *dqn.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

@@ -832,6 +832,64 @@ int sg_policy_grad_device(sg_env *env, const sg_policy *policy, int64_t n, const
 /* Bytes of workspace sg_policy_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid policy or n */
 size_t sg_policy_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int64_t n);
 
+/* Policy populations: P = `members` actor-critics of ONE architecture served by one launch per call, for hyper-parameter and seed
+ * sweeps and population-based training over many small learners on one batch of envs.  The reference has no counterpart.
+ * The parameters are stacked along a leading dimension, the layout of torch.func.stack_module_state: every weight float32
+ * [P, out, in], every bias [P, out], log_std [P, 2], each contiguous.  The calls take an ordinary sg_policy, and an ordinary sg_policy_grads, whose
+ * pointers address member 0 -- the start of each stacked tensor -- and `members` beside it; member m's tensor is at pointer + m x
+ * numel(tensor).  sg_policy keeps its size and reserved stays 0.  An optimizer step, or a copy of one member's slices over another's
+ * (PBT's exploit step), is seen by the next call.
+ * Member m owns the contiguous block of rows [m n, (m + 1) n): in the act and rollout calls n = num_envs / members of the handle's
+ * local envs (members must divide num_envs; the block is by the env's index WITHIN the handle, while the noise stays keyed by the
+ * global index env_index_base + i, stream tag 5, exactly as sg_policy_act_device's), in the evaluate and grad calls n is the argument.
+ * Arithmetic: none of its own.  One workgroup serves one member and runs sg_policy's kernels' device functions on that member's rows
+ * with that member's parameters: every output row of member m is bit for bit what the single-policy call gives for that row with an
+ * sg_policy over member m's slices (for the act call: on a handle in which the env has the same global index).
+ * Scope: the on-policy family only (sg_policy, continuous and discrete ids); sg_qnet, sg_squashed_policy and sg_dqn have no
+ * population calls.
+ * Refused by every call (SG_ERR_INVALID, with a message, nothing enqueued): whatever sg_policy_act_device refuses of the policy;
+ * members < 1 or members > 65535; then what the single-policy call of the same name refuses. */
+/* sg_policy_act_device for `members` members: obs_dev [num_envs, obs_dim]; action_out, logp_out, value_out as there, row i by member
+ * i / (num_envs / members).  One launch.  Refused also: members not dividing num_envs. */
+int sg_policy_population_act_device(sg_env *env, const sg_policy *policy, int32_t members, const float *obs_dev, uint64_t seed,
+                                    uint64_t step, int32_t deterministic, void *action_out, float *logp_out, float *value_out,
+                                    void *hip_stream);
+/* sg_rollout_policy_device for `members` members: the same buffers, the same loop -- for every t the population act launch with step =
+ * first_step + t, then the single step sg_step_device enqueues -- then one critic-only population launch for value[n_steps]; every
+ * output is bit for bit what the hand-written loop of sg_policy_population_act_device and sg_step_device gives.  terminal_list (may be
+ * NULL) is filled exactly as sg_rollout_policy_device fills it (observation records).
+ * terminal_value is served DENSE here: float32 [n_steps, num_envs], the form sg_gae_device reads "only where done and trunc are both
+ * set"; when given, every step adds one critic-only population launch over that step's dense terminal rows (sg_step_device's
+ * terminal_obs, normalized like them), with or without a list.  terminal_value[t, i] is V, under env i's member, of the last
+ * observation of the episode env i finished at step t; rows of envs that did not finish at step t hold UNSPECIFIED values.  A
+ * list-shaped terminal_value ([capacity], one per record) is not served: a record's member varies from lane to lane.
+ * Refused as sg_policy_population_act_device refuses, and: n_steps < 1, a null obs, action, reward, done or truncated, a value or
+ * terminal_value without a critic, an incomplete list. */
+int sg_rollout_policy_population_device(sg_env *env, int32_t n_steps, const sg_policy *policy, int32_t members, uint64_t seed,
+                                        uint64_t first_step, int32_t deterministic, float *obs, void *action, float *logp, float *value,
+                                        float *reward, uint8_t *done, uint8_t *truncated, const sg_terminal_list *terminal_list,
+                                        float *terminal_value, void *hip_stream);
+/* sg_policy_evaluate_device for `members` members on n rows each: obs float32 [members, n, obs_dim], action float32 [members, n, 2]
+ * (discrete ids: int32 [members, n]), outputs float32 [members, n], each may be NULL.  One launch.  Refused also: members x n above
+ * 2^31 - 1. */
+int sg_policy_population_evaluate_device(sg_env *env, const sg_policy *policy, int32_t members, int64_t n, const float *obs,
+                                         const void *action, float *logp_out, float *entropy_out, float *value_out, void *hip_stream);
+/* sg_policy_grad_device for `members` members on n rows each: g_* float32 [members, n] (each may be NULL); grads holds the pointers of
+ * STACKED gradient tensors of the parameters' shapes ([members, out, in], [members, out], [members, 2]), addressed at member 0 like
+ * the policy's; WRITTEN, not accumulated.  sg_policy_grad_device's scheme per member: partial sums workspace[m][group][parameter], a
+ * reduction in group order, no atomics -- the same inputs and the same n give the same bits.  A member's rows go to
+ *     G = min(ceil(n / R), max(1, 256 / members))   (integer division)
+ * workgroups of R rows (R as sg_policy_grad_device's: 256, 128 or 64 by the hidden width), so the workspace stays within about
+ * max(256, members) x the parameters' floats.  Consequence: member m's gradient is bit for bit sg_policy_grad_device's for the same
+ * n rows and member m's parameters whenever ceil(n / R) <= 256 / members; beyond that it is the same sum in another grouping (close,
+ * not bit-equal).  Two launches.  Refused also: members x n above 2^31 - 1; a workspace smaller than
+ * sg_policy_population_grad_workspace_bytes(env, policy, members, n). */
+int sg_policy_population_grad_device(sg_env *env, const sg_policy *policy, int32_t members, int64_t n, const float *obs, const void *action,
+                                     const float *g_logp, const float *g_entropy, const float *g_value, const sg_policy_grads *grads,
+                                     void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_policy_population_grad_device needs for n rows per member; 0 and an error message for an invalid policy, members or n */
+size_t sg_policy_population_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int32_t members, int64_t n);
+
 /* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
  * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
  * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.

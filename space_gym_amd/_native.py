@@ -257,6 +257,13 @@ SYMBOLS = {
     "sg_dqn_evaluate_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_dqn_grad_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgDqnGrads), _vp, C.c_size_t, _vp]),
     "sg_dqn_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgDqn), C.c_int64]),
+    "sg_policy_population_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
+    "sg_rollout_policy_population_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp,
+                                                      _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),
+    "sg_policy_population_evaluate_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sg_policy_population_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp,
+                                                   C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
+    "sg_policy_population_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -86,12 +86,15 @@ __device__ __forceinline__ void policy_layer(const float *__restrict__ wt, const
 }
 
 // One net for this lane's observation row: head outputs 0 .. kPolicyHeadPad - 1 into `out`.  tail (the Q critics, sg_qnet.inc): the
-// last kPolicyActDim of the p.obs_dim inputs are tail[0 .. 1], the row's action, and obs_row holds the others
+// last kPolicyActDim of the p.obs_dim inputs are tail[0 .. 1], the row's action, and obs_row holds the others.  member (sg_population.inc):
+// the net's tensors are stacked [members, ...] and this is member `member`'s slice of each, at member x numel(tensor)
 template <int NT>
 __device__ __forceinline__ void policy_net(const PolicyDev &p, const PolicyNet &net, int head, const float *__restrict__ obs_row,
-                                           float *wt, float *bs, float *h, float (&out)[kPolicyHeadPad], const float *__restrict__ tail = nullptr) {
+                                           float *wt, float *bs, float *h, float (&out)[kPolicyHeadPad], const float *__restrict__ tail = nullptr,
+                                           int member = 0) {
     constexpr int J = kPolicyTile * NT;
     const int stride = (int)blockDim.x;
+    const size_t M = (size_t)member;
     const int from_obs = tail ? p.obs_dim - kPolicyActDim : p.obs_dim;
     for (int k = 0; k < from_obs; k++) h[(size_t)k * stride] = obs_row[k];
     if (tail) {
@@ -100,7 +103,7 @@ __device__ __forceinline__ void policy_net(const PolicyDev &p, const PolicyNet &
     }
     int in = p.obs_dim;
     for (int l = 0; l < p.n_hidden; l++) {  // (wave-uniform)
-        policy_stage<J>(wt, bs, net.w[l], net.b[l], in, p.hidden);
+        policy_stage<J>(wt, bs, net.w[l] + M * p.hidden * in, net.b[l] + M * p.hidden, in, p.hidden);
         float acc[J];
         policy_layer<J>(wt, bs, h, stride, in, acc);
         // (the padded outputs are activation(0) = 0 and are never read: the next layer takes p.hidden inputs)
@@ -108,35 +111,15 @@ __device__ __forceinline__ void policy_net(const PolicyDev &p, const PolicyNet &
         for (int j = 0; j < J; j++) h[(size_t)j * stride] = p.relu ? (acc[j] < 0.0f ? 0.0f : acc[j]) : policy_tanh(acc[j]);  // (a NaN stays one)
         in = p.hidden;
     }
-    policy_stage<kPolicyHeadPad>(wt, bs, net.w[p.n_hidden], net.b[p.n_hidden], in, head);
+    policy_stage<kPolicyHeadPad>(wt, bs, net.w[p.n_hidden] + M * head * in, net.b[p.n_hidden] + M * head, in, head);
     policy_layer<kPolicyHeadPad>(wt, bs, h, stride, in, out);
 }
 
-// flags: 1 actor (action, logp), 2 critic (value), 4 deterministic
-template <int NT>
-__global__ __launch_bounds__(policy_block(NT)) void policy_act_kernel(const SgDev *__restrict__ cfg, PolicyDev p, PolicyRows rows,
-                                                                      const float *__restrict__ obs, uint32_t seed_lo, uint32_t seed_hi,
-                                                                      uint64_t step, int flags, void *__restrict__ action_out,
-                                                                      float *__restrict__ logp_out, float *__restrict__ value_out) {
-    extern __shared__ __attribute__((aligned(16))) float sg_policy_lds[];
-    constexpr int J = kPolicyTile * NT;
-    const int n = rows.count ? (int)min(*rows.count, rows.capacity) : rows.n;
-    const int first = (int)blockIdx.x * (int)blockDim.x;
-    if (first >= n) return;  // (the whole workgroup: no barrier is left waiting)
-    const int i = first + (int)threadIdx.x;
-    const bool live = i < n;
-    const float *obs_row = obs + (size_t)(live ? i : n - 1) * p.obs_dim;  // idle lanes of the last workgroup redo its last row
-    float *wt = sg_policy_lds;
-    float *bs = wt + (size_t)max(p.hidden, p.obs_dim) * (J + kPolicyRowPad);
-    float *h = bs + J + threadIdx.x;
-    float out[kPolicyHeadPad];
-    if (flags & 2) {
-        policy_net<NT>(p, p.critic, 1, obs_row, wt, bs, h, out);
-        if (live) value_out[i] = out[0];
-    }
-    if (!(flags & 1)) return;
-    policy_net<NT>(p, p.actor, p.head, obs_row, wt, bs, h, out);
-    if (!live) return;
+// The act tail of a live row: draws (or not: flags & 4), the action and its log-prob from the actor's head outputs.  i is the env's index
+// within the handle: it keys the noise (env_index_base + i) and addresses action_out / logp_out.  log_std: the row's policy's
+__device__ __forceinline__ void policy_act_tail(const SgDev *__restrict__ cfg, const PolicyDev &p, const float *__restrict__ log_std,
+                                                const float (&out)[kPolicyHeadPad], int i, uint32_t seed_lo, uint32_t seed_hi, uint64_t step,
+                                                int flags, void *__restrict__ action_out, float *__restrict__ logp_out) {
     const bool det = (flags & 4) != 0;
     uint32_t o[4] = {0u, 0u, 0u, 0u};
     if (!det) philox4x32_10(seed_lo, seed_hi, cfg->env_index_base + (uint32_t)i, (uint32_t)step, (uint32_t)(step >> 32), kStreamPolicy, o);
@@ -172,11 +155,39 @@ __global__ __launch_bounds__(policy_block(NT)) void policy_act_kernel(const SgDe
         float lp = 0.0f, act[kPolicyActDim];
 #pragma unroll
         for (int d = 0; d < kPolicyActDim; d++) {
-            const float ls = p.log_std[d];
+            const float ls = log_std[d];
             act[d] = fmaf(expf(ls), eps[d], out[d]);
             lp += (-0.5f * eps[d] * eps[d] - ls) - 0.9189385332046727f;
         }
         reinterpret_cast<float2 *>(action_out)[i] = make_float2(act[0], act[1]);
         if (logp_out) logp_out[i] = lp;
     }
+}
+
+// flags: 1 actor (action, logp), 2 critic (value), 4 deterministic
+template <int NT>
+__global__ __launch_bounds__(policy_block(NT)) void policy_act_kernel(const SgDev *__restrict__ cfg, PolicyDev p, PolicyRows rows,
+                                                                      const float *__restrict__ obs, uint32_t seed_lo, uint32_t seed_hi,
+                                                                      uint64_t step, int flags, void *__restrict__ action_out,
+                                                                      float *__restrict__ logp_out, float *__restrict__ value_out) {
+    extern __shared__ __attribute__((aligned(16))) float sg_policy_lds[];
+    constexpr int J = kPolicyTile * NT;
+    const int n = rows.count ? (int)min(*rows.count, rows.capacity) : rows.n;
+    const int first = (int)blockIdx.x * (int)blockDim.x;
+    if (first >= n) return;  // (the whole workgroup: no barrier is left waiting)
+    const int i = first + (int)threadIdx.x;
+    const bool live = i < n;
+    const float *obs_row = obs + (size_t)(live ? i : n - 1) * p.obs_dim;  // idle lanes of the last workgroup redo its last row
+    float *wt = sg_policy_lds;
+    float *bs = wt + (size_t)max(p.hidden, p.obs_dim) * (J + kPolicyRowPad);
+    float *h = bs + J + threadIdx.x;
+    float out[kPolicyHeadPad];
+    if (flags & 2) {
+        policy_net<NT>(p, p.critic, 1, obs_row, wt, bs, h, out);
+        if (live) value_out[i] = out[0];
+    }
+    if (!(flags & 1)) return;
+    policy_net<NT>(p, p.actor, p.head, obs_row, wt, bs, h, out);
+    if (!live) return;
+    policy_act_tail(cfg, p, p.log_std, out, i, seed_lo, seed_hi, step, flags, action_out, logp_out);
 }

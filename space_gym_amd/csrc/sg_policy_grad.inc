@@ -57,8 +57,9 @@ struct PolicyScore {
     float logp, entropy;
     float dz[kPolicyHeadPad];  // d (g_logp logp + g_entropy entropy) / d head output j; continuous: [2 + d] = the same by log_std_d
 };
-__device__ __forceinline__ void policy_score(const PolicyDev &p, const float (&out)[kPolicyHeadPad], const void *__restrict__ action, int i,
-                                             float gl, float ge, bool want_grad, PolicyScore &s) {
+// log_std: the row's policy's (a population member's slice)
+__device__ __forceinline__ void policy_score(const PolicyDev &p, const float *__restrict__ log_std, const float (&out)[kPolicyHeadPad],
+                                             const void *__restrict__ action, int i, float gl, float ge, bool want_grad, PolicyScore &s) {
 #pragma unroll
     for (int j = 0; j < kPolicyHeadPad; j++) s.dz[j] = 0.0f;
     if (p.discrete) {
@@ -94,7 +95,7 @@ __device__ __forceinline__ void policy_score(const PolicyDev &p, const float (&o
         float lp = 0.0f, ent = 2.8378770664093453f;  // 1 + ln(2 pi)
 #pragma unroll
         for (int d = 0; d < kPolicyActDim; d++) {
-            const float ls = p.log_std[d], inv = expf(-ls), z = (a[d] - out[d]) * inv;
+            const float ls = log_std[d], inv = expf(-ls), z = (a[d] - out[d]) * inv;
             lp += (-0.5f * z * z - ls) - 0.9189385332046727f;
             ent += ls;
             if (want_grad) {
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(policy_block(NT)) void policy_evaluate_kernel(Polic
     policy_net<NT>(p, p.actor, p.head, obs_row, wt, bs, h, out);
     if (!live) return;
     PolicyScore s;
-    policy_score(p, out, action, i, 0.0f, 0.0f, false, s);
+    policy_score(p, p.log_std, out, action, i, 0.0f, 0.0f, false, s);
     if (logp_out) logp_out[i] = s.logp;
     if (entropy_out) entropy_out[i] = s.entropy;
 }
@@ -201,14 +202,18 @@ __device__ __forceinline__ void policy_grad_weights(const float *__restrict__ dz
 //            altogether for the idle lanes of the last tile)
 //   weights  false: the parameters' sums are not wanted, no MFMA runs and `part` is not touched
 //   want_dx  dx receives W0[:, in - 2 .. in)^T dz0, this row's gradient by the tail (else dx is left as it is)
+//   member   (sg_population.inc) the net's tensors are stacked [members, ...]: member `member`'s slice of each, at member x numel(tensor)
 template <int NT, typename HeadDz>
 __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, int head, int extra, const float *__restrict__ obs_row,
                                                 const float *__restrict__ tail, HeadDz head_dz, const PolicyGradLayout &lay,
                                                 float *__restrict__ part, bool first, bool weights, bool want_dx, float (&dx)[kPolicyActDim], float *wt,
-                                                float *bs, float *store) {
+                                                float *bs, float *store, int member = 0) {
     constexpr int C = kPolicyGradChunk;
     const PolicyNet &net = which ? p.critic : p.actor;
     const int R = (int)blockDim.x, S = R + 2, tid = (int)threadIdx.x, D = p.obs_dim, H = p.hidden, L = p.n_hidden;
+    const size_t M = (size_t)member;
+    const auto w_of = [&](int l) { return net.w[l] + M * (l == L ? head : H) * (l == 0 ? D : H); };
+    const auto b_of = [&](int l) { return net.b[l] + M * (l == L ? head : H); };
     const int from_obs = tail ? D - kPolicyActDim : D;
     __syncthreads();  // the store is free: every wave has finished the net before
     for (int k = 0; k < from_obs; k++) store[(size_t)k * S + tid] = obs_row[k];
@@ -224,7 +229,7 @@ __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, i
 #pragma unroll
         for (int c = 0; c < NT; c++) {
             if (c * C >= H) break;  // (uniform)
-            policy_stage<C>(wt, bs, net.w[l] + (size_t)c * C * in, net.b[l] + c * C, in, H - c * C);
+            policy_stage<C>(wt, bs, w_of(l) + (size_t)c * C * in, b_of(l) + c * C, in, H - c * C);
             float acc[C];
             policy_layer<C>(wt, bs, hin, S, in, acc);
 #pragma unroll
@@ -235,7 +240,7 @@ __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, i
         in = H;
     }
     float out[kPolicyHeadPad], dz_head[kPolicyHeadPad];
-    policy_stage<kPolicyHeadPad>(wt, bs, net.w[L], net.b[L], in, head);
+    policy_stage<kPolicyHeadPad>(wt, bs, w_of(L), b_of(L), in, head);
     policy_layer<kPolicyHeadPad>(wt, bs, hin, S, in, out);
     head_dz(out, dz_head);
     float *hd = store + (size_t)(D + L * H) * S;
@@ -252,7 +257,7 @@ __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, i
         if (l == 0) {
             if (want_dx) {  // one step further, for the tail's two columns of W0 only (out_l = H rows of the staging area: it holds max(H, D))
                 constexpr int A = 4;  // kPolicyActDim padded to policy_layer's four outputs
-                policy_stage_plain<A>(wt, bs, net.w[0], in_l, out_l, in_l - kPolicyActDim);
+                policy_stage_plain<A>(wt, bs, w_of(0), in_l, out_l, in_l - kPolicyActDim);
                 float acc[A];
                 policy_layer<A>(wt, bs, dz + tid, S, out_l, acc);
 #pragma unroll
@@ -263,7 +268,7 @@ __device__ __forceinline__ void policy_grad_net(const PolicyDev &p, int which, i
 #pragma unroll
         for (int c = 0; c < NT; c++) {
             if (c * C >= in_l) break;  // (uniform)
-            policy_stage_plain<C>(wt, bs, net.w[l], in_l, out_l, c * C);  // (its first barrier: every wave is past the MFMA reads of hprev)
+            policy_stage_plain<C>(wt, bs, w_of(l), in_l, out_l, c * C);  // (its first barrier: every wave is past the MFMA reads of hprev)
             float acc[C];
             policy_layer<C>(wt, bs, dz + tid, S, out_l, acc);
 #pragma unroll
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(policy_grad_block(NT)) void policy_grad_kernel(Poli
         policy_grad_net<NT>(p, 0, p.head, p.discrete ? 0 : kPolicyActDim, obs_row, nullptr,
                             [&](const float (&out)[kPolicyHeadPad], float (&dz)[kPolicyHeadPad]) {
             PolicyScore s;
-            policy_score(p, out, action, row, gl, ge, true, s);
+            policy_score(p, p.log_std, out, action, row, gl, ge, true, s);
 #pragma unroll
             for (int j = 0; j < kPolicyHeadPad; j++) dz[j] = s.dz[j];
         }, lay, part, first, true, false, no_dx, wt, bs, store);
@@ -317,10 +322,10 @@ __global__ __launch_bounds__(policy_grad_block(NT)) void policy_grad_kernel(Poli
     }
 }
 
-// grads[e] = ws[0][e] + ws[1][e] + ... in workgroup order
-__global__ __launch_bounds__(256) void policy_grad_reduce_kernel(const float *__restrict__ ws, int parts, int total, PolicyGradOut o) {
-    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= total) return;
+// Element e of the partial sums ws[parts][total], added in workgroup order, to its place in the segment's tensor; member (sg_population.inc):
+// the tensors are stacked [members, ...] and this is member `member`'s slice
+__device__ __forceinline__ void policy_grad_reduce_element(const float *__restrict__ ws, int parts, int total, const PolicyGradOut &o, int e,
+                                                           int member) {
     int s = 0;
     while (s + 1 < o.count && e >= o.off[s + 1]) s++;
     if (!o.dst[s]) return;
@@ -329,5 +334,12 @@ __global__ __launch_bounds__(256) void policy_grad_reduce_kernel(const float *__
         sum = ws[e];
         for (int g = 1; g < parts; g++) sum += ws[(size_t)g * total + e];
     }
-    o.dst[s][e - o.off[s]] = sum;
+    o.dst[s][(size_t)member * (o.off[s + 1] - o.off[s]) + (e - o.off[s])] = sum;
+}
+
+// grads[e] = ws[0][e] + ws[1][e] + ... in workgroup order
+__global__ __launch_bounds__(256) void policy_grad_reduce_kernel(const float *__restrict__ ws, int parts, int total, PolicyGradOut o) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= total) return;
+    policy_grad_reduce_element(ws, parts, total, o, e, 0);
 }

@@ -146,6 +146,8 @@ class MultiDeviceVectorEnv:
     squashed_sample_torch = squashed_sample_raw_torch = squashed_grad_torch = _no_policy
     dqn_torch = dqn_act_torch = rollout_dqn_torch = _no_policy
     dqn_evaluate_torch = dqn_evaluate_raw_torch = dqn_grad_torch = _no_policy
+    policy_population_torch = population_member_torch = population_act_torch = rollout_population_torch = _no_policy
+    population_evaluate_torch = population_evaluate_raw_torch = population_grad_torch = _no_policy
 
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)

@@ -146,6 +146,8 @@ class ShardedVectorEnv:
     squashed_sample_torch = squashed_sample_raw_torch = squashed_grad_torch = _no_policy
     dqn_torch = dqn_act_torch = rollout_dqn_torch = _no_policy
     dqn_evaluate_torch = dqn_evaluate_raw_torch = dqn_grad_torch = _no_policy
+    policy_population_torch = population_member_torch = population_act_torch = rollout_population_torch = _no_policy
+    population_evaluate_torch = population_evaluate_raw_torch = population_grad_torch = _no_policy
 
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""

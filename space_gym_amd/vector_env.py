@@ -174,9 +174,22 @@ class Dqn:
         self.workspace = None  # dqn_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
+class PolicyPopulation:
+    """What policy_population_torch returns: the sg_policy struct (include/spacegym.h) over the caller's STACKED parameter tensors
+    (weight [P, out, in], bias [P, out], log_std [P, 2]; its pointers address member 0), which it keeps alive; members, n_hidden,
+    hidden, activation and has_critic describe the nets."""
+
+    def __init__(self, struct, tensors, has_critic, members):
+        self.struct, self.tensors, self.has_critic, self.members = struct, tuple(tensors), bool(has_critic), int(members)
+        self.n_hidden, self.hidden = int(struct.n_hidden), int(struct.hidden)
+        self.activation = "relu" if struct.activation else "tanh"
+        self.workspace = None  # population_grad_torch's partial sums: a uint8 tensor, grown on demand
+
+
 # per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id (Dqn: a continuous one)
 _NET_HANDLES = {Policy: ("policy", "policy_torch", "a = mean + exp(log_std) eps"), QNet: ("q", "q_torch", "the Q critics"),
-                SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor"), Dqn: ("dqn", "dqn_torch", "the DQN head Q(obs) -> 6")}
+                SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor"), Dqn: ("dqn", "dqn_torch", "the DQN head Q(obs) -> 6"),
+                PolicyPopulation: ("pop", "policy_population_torch", "a = mean + exp(log_std) eps")}
 
 
 def _activation_code(activation):
@@ -196,6 +209,44 @@ _Q_EVALUATE = None
 _POLICY_ACTION = None
 _SQUASHED_SAMPLE = None
 _DQN_EVALUATE = None
+_POPULATION_EVALUATE = None
+
+
+def _population_evaluate_function():
+    """the torch.autograd.Function behind population_evaluate_torch"""
+    global _POPULATION_EVALUATE
+    if _POPULATION_EVALUATE is not None:
+        return _POPULATION_EVALUATE
+    import torch
+
+    class PopulationEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, env, pop, obs, action, *params):
+            ctx.env, ctx.pop = env, pop
+            ctx.save_for_backward(obs, action)
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
+            logp, entropy, value = env.population_evaluate_raw_torch(pop, obs, action)
+            return logp, entropy, value
+
+        @staticmethod
+        def backward(ctx, g_logp, g_entropy, g_value=None):
+            env, pop = ctx.env, ctx.pop
+            none = (None,) * (4 + len(pop.tensors))
+            if (g_logp is None and g_entropy is None and g_value is None) or not any(ctx.needs_input_grad[4:]):
+                return none
+            obs, action = ctx.saved_tensors
+            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            out = env.population_grad_torch(pop, obs, action, con(g_logp), con(g_entropy), con(g_value) if pop.has_critic else None)
+            L = pop.n_hidden + 1
+            grads = [t for pair in out["actor"] for t in pair]
+            if pop.has_critic:
+                grads += [t for pair in out["critic"] for t in pair] if out["critic"] is not None else [None] * (2 * L)
+            if out["log_std"] is not None:
+                grads.append(out["log_std"])
+            return (None, None, None, None, *grads)
+
+    _POPULATION_EVALUATE = PopulationEvaluate
+    return PopulationEvaluate
 
 
 def _dqn_evaluate_function():
@@ -1362,11 +1413,12 @@ class SpaceGymVectorEnv:
             self._check_tensor(f"{name}[{l}] bias", b, torch.float32, tuple(like[2 * l + 1].shape))
             mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
 
-    def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None):
-        """the workspace tensor cached on a Policy / QNet / SquashedPolicy / Dqn handle, grown when n needs more -- never inside a capture;
-        refused: what the error names when the engine refuses the net or n (default: who)"""
+    def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None, members=None):
+        """the workspace tensor cached on a Policy / QNet / SquashedPolicy / Dqn / PolicyPopulation handle, grown when n needs more -- never
+        inside a capture; refused: what the error names when the engine refuses the net or n (default: who); members: a population's,
+        which its query takes before n"""
         import torch
-        need = int(getattr(self._lib, bytes_fn)(self._h, C.byref(handle.struct), n))
+        need = int(getattr(self._lib, bytes_fn)(self._h, C.byref(handle.struct), *((n,) if members is None else (members, n))))
         if need == 0:
             self._ck(-1, refused or who)
         ws = handle.workspace
@@ -1559,6 +1611,224 @@ class SpaceGymVectorEnv:
         torch.no_grad(), or when no parameter requires grad, it is the plain forward.  value is None without a critic."""
         self._net_rows(policy, Policy, obs, action=action)
         return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
+
+    # ------------------------------------------------------------------ policy populations: P stacked actor-critics on P env blocks per launch
+    def _stacked_layers(self, name, layers, members, fan_in, out, mlp, keep):
+        """_mlp_layers for one stacked net [(weight [P, width, fan_in], bias [P, width]), ...]: the pointers address member 0"""
+        import torch
+        layers = [tuple(l) for l in layers]
+        n_hidden = len(layers) - 1
+        if not 1 <= n_hidden <= 3:
+            raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
+        w0 = layers[0][0]
+        if not isinstance(w0, torch.Tensor) or w0.dim() != 3:
+            raise ValueError(f"{name}[0]: expected a stacked weight of shape ({members}, hidden, {fan_in})")
+        hidden = int(w0.shape[1])
+        if not 1 <= hidden <= 128:
+            raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
+        for l, (w, b) in enumerate(layers):
+            width = out if l == n_hidden else hidden
+            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (members, width, fan_in))
+            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (members, width))
+            mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
+            keep.extend((w, b))
+            fan_in = hidden
+        return n_hidden, hidden
+
+    def _population(self, pop, per_env=False):
+        """checks a policy_population_torch handle; per_env: its members must divide this handle's envs"""
+        self._net_handle(pop, PolicyPopulation)
+        if per_env and self.num_envs % pop.members:
+            raise ValueError(f"pop: {pop.members} members do not divide num_envs = {self.num_envs} (member m owns the envs [m B / P, (m + 1) B / P))")
+        return pop.members
+
+    def policy_population_torch(self, members, actor, critic=None, log_std=None, activation="tanh"):
+        """A handle on a population of `members` actor-critics of one architecture whose parameters are STACKED along a leading
+        dimension, the layout of torch.func.stack_module_state, and stay where they are: actor / critic lists [(weight, bias), ...]
+        of contiguous float32 CUDA tensors, weight [P, out, in] and bias [P, out], shapes per member as policy_torch's; log_std
+        float32 [P, 2] (continuous ids).  Member m owns the contiguous env block [m B / P, (m + 1) B / P) of the handle's B envs in
+        population_act_torch / rollout_population_torch (P must divide B) and rows [m] of the [P, n, ...] tensors of the evaluate
+        and grad calls.  A PBT exploit step is W[loser].copy_(W[winner]) on the caller's tensors: the next call reads it."""
+        import torch
+        members = int(members)
+        if not 1 <= members <= 65535:
+            raise ValueError(f"members must be 1 .. 65535, got {members}")
+        if self.num_envs % members:
+            raise ValueError(f"members: {members} does not divide num_envs = {self.num_envs}")
+        head = 6 if self.discrete else 2
+        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=_activation_code(activation), head=head)
+        keep = []
+        p.n_hidden, p.hidden = self._stacked_layers("actor", actor, members, self.obs_dim, head, p.actor, keep)
+        if critic is not None:
+            if self._stacked_layers("critic", critic, members, self.obs_dim, 1, p.critic, keep) != (p.n_hidden, p.hidden):
+                raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
+        if self.discrete:
+            if log_std is not None:
+                raise ValueError("log_std: the discrete ids take none")
+        else:
+            if log_std is None:
+                raise ValueError(f"log_std: a continuous id needs the float32 [{members}, 2] log standard deviations")
+            self._check_tensor("log_std", log_std, torch.float32, (members, 2))
+            p.log_std = log_std.data_ptr()
+            keep.append(log_std)
+        return PolicyPopulation(p, keep, critic is not None, members)
+
+    def population_member_torch(self, pop, m):
+        """Member m of a population as a plain policy_torch handle over the views W[m], b[m], log_std[m] of the stacked tensors (no
+        copy): to evaluate or export one member with the single-policy calls."""
+        members = self._population(pop)
+        m = int(m)
+        if not 0 <= m < members:
+            raise ValueError(f"m: expected a member index 0 .. {members - 1}, got {m}")
+        L = pop.n_hidden + 1
+        t = pop.tensors
+        pairs = lambda ts: [(ts[2 * l][m], ts[2 * l + 1][m]) for l in range(L)]
+        return self.policy_torch(actor=pairs(t[:2 * L]), critic=pairs(t[2 * L:4 * L]) if pop.has_critic else None,
+                                 log_std=None if self.discrete else t[-1][m], activation=pop.activation)
+
+    def population_act_torch(self, pop, obs, seed=0, step=0, deterministic=False, out=None):
+        """policy_act_torch with member i // (B / P) acting for env i, in ONE launch (sg_policy_population_act_device;
+        graph-capturable): the same tensors, and per row bit for bit what policy_act_torch gives with that member's handle."""
+        import torch
+        self._population(pop, per_env=True)
+        B, D = self.num_envs, self.obs_dim
+        self._check_tensor("obs", obs, torch.float32, (B, D))
+        if out is None:
+            out = dict(action=torch.empty((B,) if self.discrete else (B, 2), dtype=torch.int32 if self.discrete else torch.float32, device=obs.device),
+                       logp=torch.empty(B, dtype=torch.float32, device=obs.device),
+                       value=torch.empty(B, dtype=torch.float32, device=obs.device) if pop.has_critic else None)
+        else:
+            if out.get("action") is None and out.get("value") is None:
+                raise ValueError("out: expected action (with logp), value, or both")
+            if out.get("action") is not None:
+                self._check_tensor("out['action']", out["action"], torch.int32 if self.discrete else torch.float32, (B,) if self.discrete else (B, 2))
+                self._check_tensor("out['logp']", out["logp"], torch.float32, (B,))
+            if out.get("value") is not None:
+                if not pop.has_critic:
+                    raise ValueError("out['value']: the population has no critic")
+                self._check_tensor("out['value']", out["value"], torch.float32, (B,))
+        action, value = out.get("action"), out.get("value")
+        logp = out.get("logp") if action is not None else None
+        self._ck(self._lib.sg_policy_population_act_device(self._h, C.byref(pop.struct), pop.members, _ptr(obs), int(seed), int(step),
+                                                           int(bool(deterministic)), _ptr(action), _ptr(logp), _ptr(value), self._stream()),
+                 "sg_policy_population_act_device")
+        return action, logp, value
+
+    def rollout_population_torch(self, pop, obs, action, logp, value, reward, done, trunc, seed=0, first_step=0, deterministic=False,
+                                 terminal=None, terminal_value=None):
+        """rollout_policy_torch with a population acting (sg_rollout_policy_population_device): the same tensors, bit for bit the loop
+        of population_act_torch and step_torch.  terminal: a terminal_list_torch dict, filled like rollout_torch's (observation
+        records; no terminal["value"]: a record's member varies).  terminal_value: float32 [K, B], DENSE -- entry (t, i) is V, under
+        env i's member, of the last observation of the episode env i finished at step t, and unspecified elsewhere; it is
+        gae_torch's terminal_value as it stands:
+            env.gae_torch(reward, done, trunc, value[:-1], value[-1], terminal_value=terminal_value)"""
+        import torch
+        self._population(pop, per_env=True)
+        if not isinstance(action, torch.Tensor) or action.dim() < 2 or int(action.shape[0]) < 1:
+            raise ValueError("action: expected a CUDA tensor of at least one step")
+        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
+        if pop.has_critic and value is None:
+            raise ValueError("value: the population has a critic; pass the float32 [K + 1, B] tensor its values go to")
+        if not pop.has_critic and (value is not None or terminal_value is not None):
+            raise ValueError("value / terminal_value: the population has no critic")
+        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
+        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
+        self._check_tensor("logp", logp, torch.float32, (K, B))
+        if value is not None:
+            self._check_tensor("value", value, torch.float32, (K + 1, B))
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        if terminal_value is not None:
+            self._check_tensor("terminal_value", terminal_value, torch.float32, (K, B))
+        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
+        self._ck(self._lib.sg_rollout_policy_population_device(
+            self._h, K, C.byref(pop.struct), pop.members, int(seed), int(first_step), int(bool(deterministic)), _ptr(obs), _ptr(action),
+            _ptr(logp), _ptr(value), _ptr(reward), _ptr(done), _ptr(trunc), C.byref(tl) if tl is not None else None, _ptr(terminal_value),
+            self._stream()), "sg_rollout_policy_population_device")
+        return obs, action, logp, value, reward, done, trunc
+
+    def _population_rows(self, pop, obs, action):
+        """checks (pop, obs [P, n, D], action [P, n, 2] or int32 [P, n]) and returns (P, n)"""
+        import torch
+        P = self._population(pop)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or int(obs.shape[1]) < 1:
+            raise ValueError(f"obs: expected a CUDA tensor of shape ({P}, n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[1])
+        self._check_tensor("obs", obs, torch.float32, (P, n, self.obs_dim))
+        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (P, n) if self.discrete else (P, n, 2))
+        return P, n
+
+    def population_evaluate_raw_torch(self, pop, obs, action, out=None):
+        """policy_evaluate_raw_torch for every member on its own n rows in ONE launch (sg_policy_population_evaluate_device): obs
+        float32 [P, n, D], action float32 [P, n, 2] (discrete ids: int32 [P, n]) -> (logp, entropy, value) float32 [P, n]; row [m] is
+        bit for bit policy_evaluate_raw_torch(population_member_torch(pop, m), obs[m], action[m]).  out as there."""
+        import torch
+        P, n = self._population_rows(pop, obs, action)
+        if out is None:
+            out = {k: torch.empty((P, n), dtype=torch.float32, device=obs.device) for k in (("logp", "entropy", "value") if pop.has_critic else ("logp", "entropy"))}
+        else:
+            if out.get("value") is not None and not pop.has_critic:
+                raise ValueError("out['value']: the population has no critic")
+            if all(out.get(k) is None for k in ("logp", "entropy", "value")):
+                raise ValueError("out: expected at least one of logp, entropy, value")
+            for k in ("logp", "entropy", "value"):
+                if out.get(k) is not None:
+                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (P, n))
+        self._ck(self._lib.sg_policy_population_evaluate_device(self._h, C.byref(pop.struct), P, n, _ptr(obs), _ptr(action), _ptr(out.get("logp")),
+                                                                _ptr(out.get("entropy")), _ptr(out.get("value")), self._stream()),
+                 "sg_policy_population_evaluate_device")
+        return out.get("logp"), out.get("entropy"), out.get("value")
+
+    def population_grad_torch(self, pop, obs, action, g_logp=None, g_entropy=None, g_value=None, out=None):
+        """policy_grad_torch for every member on its own n rows (sg_policy_population_grad_device: two launches, graph-capturable
+        after one warm-up call with the same n): g_* float32 [P, n] (None: zeros) -> a dict actor / critic / log_std as
+        policy_grad_torch's, of STACKED gradient tensors of the parameters' shapes, WRITTEN, not accumulated.  Member m's slices are bit
+        for bit policy_grad_torch's for the same rows with member m's handle while ceil(n / R) <= 256 // P (R = 256, 128 or 64 rows
+        by the hidden width); beyond that they are the same sums in another grouping.  Same inputs and same n: the same bits."""
+        import torch
+        P, n = self._population_rows(pop, obs, action)
+        for name, g in (("g_logp", g_logp), ("g_entropy", g_entropy), ("g_value", g_value)):
+            if g is not None:
+                self._check_tensor(name, g, torch.float32, (P, n))
+        if g_value is not None and not pop.has_critic:
+            raise ValueError("g_value: the population has no critic")
+        L = pop.n_hidden + 1
+        params = pop.tensors
+        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if pop.has_critic else ()
+        if out is None:
+            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if g_value is not None else None,
+                       log_std=None if self.discrete else torch.empty_like(params[-1]))
+        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
+        if out.get("critic") is not None:
+            if not pop.has_critic:
+                raise ValueError("out['critic']: the population has no critic")
+            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
+        elif g_value is not None:
+            raise ValueError("out['critic']: g_value is given; the critic's gradients need tensors")
+        if self.discrete:
+            if out.get("log_std") is not None:
+                raise ValueError("out['log_std']: the discrete ids have none")
+        else:
+            if out.get("log_std") is None:
+                raise ValueError(f"out['log_std']: expected a float32 [{P}, 2] tensor")
+            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (P, 2))
+            g.log_std = out["log_std"].data_ptr()
+        ws = self._grad_workspace(pop, "sg_policy_population_grad_workspace_bytes", n, obs.device, "population_grad_torch",
+                                  "sg_policy_population_grad_workspace_bytes", members=P)
+        self._ck(self._lib.sg_policy_population_grad_device(self._h, C.byref(pop.struct), P, n, _ptr(obs), _ptr(action), _ptr(g_logp), _ptr(g_entropy),
+                                                            _ptr(g_value), C.byref(g), _ptr(ws), ws.numel(), self._stream()),
+                 "sg_policy_population_grad_device")
+        return out
+
+    def population_evaluate_torch(self, pop, obs, action):
+        """logp, entropy, value, each [P, n], of the stored rows under the CURRENT parameters, differentiable with respect to the
+        stacked tensors the handle holds: ONE torch.autograd.Function over population_evaluate_raw_torch whose backward is one
+        population_grad_torch call (a None g for an output the loss did not use).  A loss summed over the members' losses gives every
+        member its own gradient in its slices; .grad accumulates as usual.  value is None without a critic."""
+        self._population_rows(pop, obs, action)
+        return _population_evaluate_function().apply(self, pop, obs, action, *pop.tensors)
 
     # ------------------------------------------------------------------ the off-policy learner's nets: twin Q critics, action gradients
     def q_torch(self, critics, activation="relu"):

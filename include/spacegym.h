@@ -832,6 +832,76 @@ int sg_policy_grad_device(sg_env *env, const sg_policy *policy, int64_t n, const
 /* Bytes of workspace sg_policy_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid policy or n */
 size_t sg_policy_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int64_t n);
 
+/* The PPO minibatch update in one call: from stored rollout rows and a minibatch index to the parameter gradients and the loss
+ * statistics -- the gathers, sg_policy_evaluate_device, the loss and sg_policy_grad_device of a hand-composed update, without autograd.
+ * The objective is the CleanRL / SB3 form.  For entry i of the minibatch, r = index[i] (r = i when index is NULL); logp, entropy and
+ * value are sg_policy_evaluate_device's values of row r, bit for bit:
+ *     lr = logp - old_logp[r];  ratio = exp(lr);  A = (advantage[r] - mean) * rstd when normalising, else advantage[r]
+ *     pg = max(-A ratio, -A clamp(ratio, 1 - c, 1 + c))                                        c = clip_range
+ *     vl = 0.5 max((value - ret[r])^2, (vclip - ret[r])^2),  vclip = old_value[r] + clamp(value - old_value[r], -cv, cv)
+ *          with cv = clip_range_vf > 0; otherwise vl = 0.5 (value - ret[r])^2
+ *     loss = mean(pg) - ent_coef mean(entropy) + vf_coef mean(vl)
+ * and what goes to sg_policy_grad_device's backward:
+ *     g_logp = -A ratio / n where the unclipped term is >= the clipped one, else 0;  g_entropy = -ent_coef / n
+ *     g_value = vf_coef (value - ret[r]) / n where the unclipped square is >= the clipped one; otherwise vf_coef (vclip - ret[r]) / n
+ *               inside the clamp (its bounds included) and 0 outside it
+ * -- torch's subgradients: clamp passes the gradient at its bounds; the two branches of a max tie only where both give the same
+ * derivative, or where A = 0.  clip_range = +inf is allowed and gives the unclipped policy gradient (A2C).  mean and rstd = 1 /
+ * (std + adv_epsilon) are those of advantage[index[i]], i < n, std unbiased (torch's .std()), accumulated in float64 in a fixed
+ * order and rounded to float32; everything else is float32, and (n) enters as (float)n. */
+typedef struct sg_ppo_config {
+    uint32_t struct_size;        /* sizeof(sg_ppo_config) */
+    float clip_range;            /* c > 0; +inf: no clipping.  Default 0.2 */
+    float clip_range_vf;         /* cv; <= 0: the value term is not clipped (default 0) */
+    float ent_coef;              /* >= 0, default 0 */
+    float vf_coef;               /* >= 0, default 0.5; ignored for a policy without a critic */
+    int32_t normalize_advantage; /* default 1; needs n >= 2 */
+    float adv_epsilon;           /* >= 0, default 1e-8 */
+    int32_t reserved;            /* 0 */
+} sg_ppo_config;
+void sg_ppo_config_init(sg_ppo_config *cfg);
+/* Device pointers into the flattened rollout of `rows` rows */
+typedef struct sg_ppo_batch {
+    const float *obs;        /* float32 [rows, obs_dim] */
+    const void *action;      /* float32 [rows, 2] (discrete ids: int32 [rows]) as sg_policy_act_device stored it */
+    const float *old_logp;   /* float32 [rows] */
+    const float *advantage;  /* float32 [rows] */
+    const float *ret;        /* float32 [rows]; may be NULL for a policy without a critic */
+    const float *old_value;  /* float32 [rows]; may be NULL unless clip_range_vf > 0 */
+    const int64_t *index;    /* int64 [n] rows of the minibatch, repeats allowed; NULL: rows 0 .. n - 1 */
+} sg_ppo_batch;
+/* Optional per-row outputs, float32 [n], each may be NULL: the numbers the kernel used for entry i, for tests and for learners that
+ * log them (value and g_value need a critic) */
+typedef struct sg_ppo_rows {
+    float *logp;
+    float *value;
+    float *g_logp;
+    float *g_value;
+} sg_ppo_rows;
+/* grads (an sg_policy_grads with every slot of the policy's nets given: the actor, log_std for the continuous ids, the critic when
+ * the policy has one) receives d loss / d theta, WRITTEN, not accumulated: bit for bit what sg_policy_grad_device gives at the same n
+ * for the gathered rows with row_out's g_logp / g_value and g_entropy = -ent_coef / n.
+ * stats_out float32 [12]: loss, policy_loss = mean(pg), value_loss = mean(vl) (0 without a critic), entropy = mean(entropy),
+ * approx_kl = mean((ratio - 1) - lr), old_approx_kl = mean(-lr), clip_fraction = mean(|ratio - 1| > c), adv_mean, adv_std (both 0
+ * when not normalising), bad_rows, and two reserved zeros.
+ * An index outside [0, rows) is clamped before any address is formed from it; such an entry contributes zero to every gradient and
+ * statistic (to the advantage statistics it counts as advantage 0), is counted in bad_rows, and the means still divide by n.
+ * Launches: the advantage statistics (only when normalising), the backward -- sg_policy_grad_device's kernel frame, with the critic
+ * first and the loss formed from the head outputs, every workgroup leaving its statistics sums beside its partial sums in
+ * `workspace` (at least sg_ppo_grad_workspace_bytes(env, policy, n) bytes, any content) -- and the reduction in workgroup order.
+ * Allocates nothing, never synchronises, hipGraph-capturable.  No atomics: the same inputs and the same n give the same bits.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): whatever sg_policy_act_device refuses of the policy; a null cfg, a
+ * wrong struct_size or reserved; n < 1; rows < 1; clip_range not > 0; a negative or NaN ent_coef, vf_coef or adv_epsilon; a NaN
+ * clip_range_vf; normalize_advantage with n = 1; a null batch, obs, action, old_logp or advantage; a null ret with a critic;
+ * clip_range_vf > 0 without old_value; n > rows without an index; a null stats_out; row_out's value or g_value without a critic;
+ * what sg_policy_grad_device refuses of grads; a null workspace, one smaller than the query's answer or not aligned to 8 bytes. */
+int sg_ppo_grad_device(sg_env *env, const sg_policy *policy, const sg_ppo_config *cfg, const sg_ppo_batch *batch, int64_t rows, int64_t n,
+                       const sg_policy_grads *grads, float *stats_out, const sg_ppo_rows *row_out, void *workspace, size_t workspace_bytes,
+                       void *hip_stream);
+/* Bytes of workspace sg_ppo_grad_device needs for n rows: sg_policy_grad_workspace_bytes' and the statistics partials; 0 and an error
+ * message for an invalid policy or n */
+size_t sg_ppo_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int64_t n);
+
 /* Policy populations: P = `members` actor-critics of ONE architecture served by one launch per call, for hyper-parameter and seed
  * sweeps and population-based training over many small learners on one batch of envs.  The reference has no counterpart.
  * The parameters are stacked along a leading dimension, the layout of torch.func.stack_module_state: every weight float32

@@ -117,6 +117,24 @@ class SgPolicyGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("actor", SgPolicyMlp), ("critic", SgPolicyMlp), ("log_std", C.c_void_p)]
 
 
+class SgPpoConfig(C.Structure):
+    """sg_ppo_config (include/spacegym.h): sg_ppo_config_init fills in clip_range 0.2, clip_range_vf 0 (off), ent_coef 0, vf_coef 0.5,
+    normalize_advantage 1, adv_epsilon 1e-8"""
+    _fields_ = [("struct_size", C.c_uint32), ("clip_range", C.c_float), ("clip_range_vf", C.c_float), ("ent_coef", C.c_float),
+                ("vf_coef", C.c_float), ("normalize_advantage", C.c_int32), ("adv_epsilon", C.c_float), ("reserved", C.c_int32)]
+
+
+class SgPpoBatch(C.Structure):
+    """sg_ppo_batch (include/spacegym.h): the columns of the flattened rollout and the minibatch's int64 row index"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("old_logp", C.c_void_p), ("advantage", C.c_void_p), ("ret", C.c_void_p),
+                ("old_value", C.c_void_p), ("index", C.c_void_p)]
+
+
+class SgPpoRows(C.Structure):
+    """sg_ppo_rows (include/spacegym.h): optional per-row outputs of sg_ppo_grad_device"""
+    _fields_ = [("logp", C.c_void_p), ("value", C.c_void_p), ("g_logp", C.c_void_p), ("g_value", C.c_void_p)]
+
+
 class SgQnet(C.Structure):
     """sg_qnet (include/spacegym.h): one or two Q critics on [obs | action] rows, parameters read where the learner keeps them"""
     _fields_ = [("struct_size", C.c_uint32), ("n_critics", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32),
@@ -239,6 +257,10 @@ SYMBOLS = {
     "sg_policy_evaluate_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_policy_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int64, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
     "sg_policy_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int64]),
+    "sg_ppo_config_init": (None, [C.POINTER(SgPpoConfig)]),
+    "sg_ppo_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.POINTER(SgPpoConfig), C.POINTER(SgPpoBatch), C.c_int64, C.c_int64,
+                                     C.POINTER(SgPolicyGrads), _vp, C.POINTER(SgPpoRows), _vp, C.c_size_t, _vp]),
+    "sg_ppo_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int64]),
     "sg_q_evaluate_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "sg_q_grad_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgQnetGrads), _vp, _vp, C.c_size_t, _vp]),
     "sg_q_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgQnet), C.c_int64]),

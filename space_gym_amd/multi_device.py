@@ -140,6 +140,7 @@ class MultiDeviceVectorEnv:
 
     policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
     policy_evaluate_torch = policy_evaluate_raw_torch = policy_grad_torch = _no_policy
+    ppo_grad_torch = ppo_assign_grads = _no_policy
     q_torch = q_evaluate_torch = q_evaluate_raw_torch = q_grad_torch = _no_policy
     policy_action_torch = policy_action_raw_torch = policy_action_grad_torch = _no_policy
     squashed_policy_torch = squashed_act_torch = rollout_squashed_torch = _no_policy

@@ -1612,6 +1612,120 @@ class SpaceGymVectorEnv:
         self._net_rows(policy, Policy, obs, action=action)
         return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
 
+    # ------------------------------------------------------------------ the PPO minibatch update: loss, statistics and gradients in one call
+    ppo_stats_names = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "old_approx_kl", "clip_fraction", "adv_mean", "adv_std",
+                       "bad_rows", "reserved0", "reserved1")
+
+    def ppo_grad_torch(self, policy, batch, index=None, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5,
+                       normalize_advantage=True, out=None, stats=None, rows=None):
+        """One PPO minibatch update without autograd (sg_ppo_grad_device: the gathers, the forward, the clipped loss and the backward in
+        two or three launches on torch's current stream; no host synchronisation; graph-capturable after one warm-up call with the same
+        n, which sizes the workspace kept on the handle).  batch: dict obs [rows, D] / action [rows, 2] (discrete ids: int32 [rows]) /
+        logp / advantage / ret / value (float32 [rows]) of the flattened rollout; ret may be absent without a critic, value unless
+        clip_range_vf is given.  index: int64 [n] rows of the minibatch (repeats allowed; None: all rows, in order).  The objective is the
+        CleanRL / SB3 form stated in include/spacegym.h: clip_range may be float("inf") (A2C), clip_range_vf None turns value clipping off.
+        Returns (grads, stats): grads a dict actor / critic (None without a critic) / log_std (None for the discrete ids) as
+        policy_grad_torch's, WRITTEN, not accumulated (out: such a dict of tensors to fill); stats float32 [12], named by
+        ppo_stats_names (stats: the tensor to fill).  rows: optional dict logp / value / g_logp / g_value of float32 [n] tensors that
+        receive the per-row numbers the kernel used.  ppo_assign_grads hands the gradients to an optimizer.  Same inputs and same n:
+        the same bits."""
+        import math
+        import torch
+        self._net_handle(policy, Policy)
+        if not isinstance(batch, dict):
+            raise ValueError("batch: expected a dict obs / action / logp / advantage / ret / value of flattened CUDA tensors")
+        obs = batch.get("obs")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"batch['obs']: expected a CUDA tensor of shape (rows, {self.obs_dim}) with rows >= 1")
+        R = int(obs.shape[0])
+        self._check_tensor("batch['obs']", obs, torch.float32, (R, self.obs_dim))
+        self._check_tensor("batch['action']", batch.get("action"), torch.int32 if self.discrete else torch.float32, (R,) if self.discrete else (R, 2))
+        if not clip_range > 0:
+            raise ValueError(f"clip_range: expected a value > 0 (float('inf'): no clipping), got {clip_range}")
+        if clip_range_vf is not None and not clip_range_vf > 0:
+            raise ValueError(f"clip_range_vf: expected None or a value > 0, got {clip_range_vf}")
+        for name, v in (("ent_coef", ent_coef), ("vf_coef", vf_coef)):
+            if not v >= 0 or math.isinf(v):
+                raise ValueError(f"{name}: expected a finite value >= 0, got {v}")
+        need = ["logp", "advantage"] + (["ret"] if policy.has_critic else []) + (["value"] if policy.has_critic and clip_range_vf is not None else [])
+        for k in need:
+            if batch.get(k) is None:
+                raise ValueError(f"batch['{k}']: missing" + (" (clip_range_vf is given)" if k == "value" else ""))
+            self._check_tensor(f"batch['{k}']", batch[k], torch.float32, (R,))
+        if index is None:
+            n = R
+        else:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1 or int(index.shape[0]) < 1:
+                raise ValueError("index: expected an int64 CUDA tensor of shape (n,) with n >= 1")
+            n = int(index.shape[0])
+            self._check_tensor("index", index, torch.int64, (n,))
+        if normalize_advantage and n < 2:
+            raise ValueError("normalize_advantage: needs n >= 2")
+        L = policy.n_hidden + 1
+        params = policy.tensors
+        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if policy.has_critic else ()
+        if out is None:
+            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if policy.has_critic else None,
+                       log_std=None if self.discrete else torch.empty_like(params[-1]))
+        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
+        if policy.has_critic:
+            if out.get("critic") is None:
+                raise ValueError("out['critic']: the policy has a critic; its gradients need tensors")
+            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
+        elif out.get("critic") is not None:
+            raise ValueError("out['critic']: the policy has no critic")
+        if self.discrete:
+            if out.get("log_std") is not None:
+                raise ValueError("out['log_std']: the discrete ids have none")
+        else:
+            if out.get("log_std") is None:
+                raise ValueError("out['log_std']: expected a float32 [2] tensor")
+            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
+            g.log_std = out["log_std"].data_ptr()
+        if stats is None:
+            stats = obs.new_empty(len(self.ppo_stats_names))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (len(self.ppo_stats_names),))
+        r = _native.SgPpoRows()
+        if rows is not None:
+            for k, t in rows.items():
+                if k not in ("logp", "value", "g_logp", "g_value"):
+                    raise ValueError(f"rows['{k}']: expected the keys logp, value, g_logp, g_value")
+                if t is None:
+                    continue
+                if k in ("value", "g_value") and not policy.has_critic:
+                    raise ValueError(f"rows['{k}']: the policy has no critic")
+                self._check_tensor(f"rows['{k}']", t, torch.float32, (n,))
+                setattr(r, k, t.data_ptr())
+        cfg = _native.SgPpoConfig()
+        self._lib.sg_ppo_config_init(C.byref(cfg))
+        cfg.clip_range, cfg.clip_range_vf = clip_range, clip_range_vf if clip_range_vf is not None else 0.0
+        cfg.ent_coef, cfg.vf_coef, cfg.normalize_advantage = ent_coef, vf_coef, int(bool(normalize_advantage))
+        b = _native.SgPpoBatch(obs=obs.data_ptr(), action=batch["action"].data_ptr(), old_logp=batch["logp"].data_ptr(),
+                               advantage=batch["advantage"].data_ptr(), ret=batch["ret"].data_ptr() if policy.has_critic else None,
+                               old_value=batch["value"].data_ptr() if "value" in need else None,
+                               index=index.data_ptr() if index is not None else None)
+        ws = self._grad_workspace(policy, "sg_ppo_grad_workspace_bytes", n, obs.device, "ppo_grad_torch", "sg_ppo_grad_workspace_bytes")
+        self._ck(self._lib.sg_ppo_grad_device(self._h, C.byref(policy.struct), C.byref(cfg), C.byref(b), R, n, C.byref(g), _ptr(stats),
+                                              C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()), "sg_ppo_grad_device")
+        return out, stats
+
+    @staticmethod
+    def ppo_assign_grads(policy, grads):
+        """makes ppo_grad_torch's (or policy_grad_torch's) tensors the .grad of the parameters the handle holds, so that optimizer.step()
+        follows directly; a net whose gradients are None keeps its .grad"""
+        L = policy.n_hidden + 1
+        params = policy.tensors
+        flat = [t for pair in grads["actor"] for t in pair]
+        if policy.has_critic:
+            flat += [t for pair in grads["critic"] for t in pair] if grads.get("critic") is not None else [None] * (2 * L)
+        if grads.get("log_std") is not None:
+            flat.append(grads["log_std"])
+        for p, t in zip(params, flat):
+            if t is not None:
+                p.grad = t
+
     # ------------------------------------------------------------------ policy populations: P stacked actor-critics on P env blocks per launch
     def _stacked_layers(self, name, layers, members, fan_in, out, mlp, keep):
         """_mlp_layers for one stacked net [(weight [P, width, fan_in], bias [P, width]), ...]: the pointers address member 0"""

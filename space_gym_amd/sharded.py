@@ -17,6 +17,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .vector_env import NET_METHODS
+
 
 def shard_bounds(num_envs, world_size, rank):
     """Contiguous block of global env indices owned by `rank` (remainder spread over the first ranks)."""
@@ -138,17 +140,7 @@ class ShardedVectorEnv:
         raise NotImplementedError("policy_torch / policy_act_torch / rollout_policy_torch: single-device front end only, not served by "
                                   "ShardedVectorEnv (a rank's SpaceGymVectorEnv runs a policy on its envs)")
 
-    policy_torch = policy_act_torch = rollout_policy_torch = _no_policy
-    policy_evaluate_torch = policy_evaluate_raw_torch = policy_grad_torch = _no_policy
-    ppo_grad_torch = ppo_assign_grads = _no_policy
-    q_torch = q_evaluate_torch = q_evaluate_raw_torch = q_grad_torch = _no_policy
-    policy_action_torch = policy_action_raw_torch = policy_action_grad_torch = _no_policy
-    squashed_policy_torch = squashed_act_torch = rollout_squashed_torch = _no_policy
-    squashed_sample_torch = squashed_sample_raw_torch = squashed_grad_torch = _no_policy
-    dqn_torch = dqn_act_torch = rollout_dqn_torch = _no_policy
-    dqn_evaluate_torch = dqn_evaluate_raw_torch = dqn_grad_torch = _no_policy
-    policy_population_torch = population_member_torch = population_act_torch = rollout_population_torch = _no_policy
-    population_evaluate_torch = population_evaluate_raw_torch = population_grad_torch = _no_policy
+    vars().update(dict.fromkeys(NET_METHODS, _no_policy))  # every net method of SpaceGymVectorEnv, in this class's namespace
 
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""

@@ -204,220 +204,102 @@ def _empty_pairs(like):
     return [(torch.empty_like(like[l]), torch.empty_like(like[l + 1])) for l in range(0, len(like), 2)]
 
 
-_POLICY_EVALUATE = None
-_Q_EVALUATE = None
-_POLICY_ACTION = None
-_SQUASHED_SAMPLE = None
-_DQN_EVALUATE = None
-_POPULATION_EVALUATE = None
+def _flat_grads(handle, out):
+    """the tensors of a *_grad_torch dict in the order of handle.tensors: None for every tensor of a net whose gradients are None or
+    absent (a frozen critic, the critic behind policy_action_grad_torch); log_std last, when the dict has one"""
+    if "critics" in out:
+        nets = out["critics"] or [None] * handle.n_critics
+    elif "net" in out:
+        nets = [out["net"]]
+    else:
+        nets = [out["actor"]] + ([out.get("critic")] if getattr(handle, "has_critic", False) else [])
+    flat = [t for pairs in nets for pair in (pairs if pairs is not None else [(None, None)] * (handle.n_hidden + 1)) for t in pair]
+    return flat + ([out["log_std"]] if out.get("log_std") is not None else [])
 
 
-def _population_evaluate_function():
-    """the torch.autograd.Function behind population_evaluate_torch"""
-    global _POPULATION_EVALUATE
-    if _POPULATION_EVALUATE is not None:
-        return _POPULATION_EVALUATE
+_NET_FUNCTIONS = {}  # key -> torch.autograd.Function
+
+
+def _net_function(key, forward, backward, materialize=False):
+    """The torch.autograd.Function `key` behind a *_torch method, made on first use (torch is imported lazily); its inputs are
+    (env, handle, obs, col, *handle.tensors), col the column beside obs (action or eps; may be None).  forward(env, handle, obs, col)
+    gives the outputs.  backward(env, handle, obs, col, needs, *gs) -- needs: whether col and each tensor need a gradient; gs: the
+    outputs' gradients, float32 and contiguous -- returns the gradients of (col, *handle.tensors), or None where there is nothing to
+    compute.  materialize False: the g of an output the loss does not use arrives as None (a NULL g), not as zeros."""
+    if key in _NET_FUNCTIONS:
+        return _NET_FUNCTIONS[key]
     import torch
 
-    class PopulationEvaluate(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, pop, obs, action, *params):
-            ctx.env, ctx.pop = env, pop
-            ctx.save_for_backward(obs, action)
-            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
-            logp, entropy, value = env.population_evaluate_raw_torch(pop, obs, action)
-            return logp, entropy, value
+    def fwd(ctx, env, handle, obs, col, *params):
+        ctx.env, ctx.handle, ctx.has_col = env, handle, col is not None
+        ctx.save_for_backward(*((obs, col) if col is not None else (obs,)))
+        if not materialize:
+            ctx.set_materialize_grads(False)
+        return forward(env, handle, obs, col)
 
-        @staticmethod
-        def backward(ctx, g_logp, g_entropy, g_value=None):
-            env, pop = ctx.env, ctx.pop
-            none = (None,) * (4 + len(pop.tensors))
-            if (g_logp is None and g_entropy is None and g_value is None) or not any(ctx.needs_input_grad[4:]):
-                return none
-            obs, action = ctx.saved_tensors
-            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            out = env.population_grad_torch(pop, obs, action, con(g_logp), con(g_entropy), con(g_value) if pop.has_critic else None)
-            L = pop.n_hidden + 1
-            grads = [t for pair in out["actor"] for t in pair]
-            if pop.has_critic:
-                grads += [t for pair in out["critic"] for t in pair] if out["critic"] is not None else [None] * (2 * L)
-            if out["log_std"] is not None:
-                grads.append(out["log_std"])
-            return (None, None, None, None, *grads)
+    def bwd(ctx, *gs):
+        col = ctx.saved_tensors[1] if ctx.has_col else None
+        gs = [None if g is None else g.to(torch.float32).contiguous() for g in gs]
+        grads = backward(ctx.env, ctx.handle, ctx.saved_tensors[0], col, ctx.needs_input_grad[3:], *gs)
+        return (None, None, None, *(grads if grads is not None else (None,) * (1 + len(ctx.handle.tensors))))
 
-    _POPULATION_EVALUATE = PopulationEvaluate
-    return PopulationEvaluate
+    _NET_FUNCTIONS[key] = type(key, (torch.autograd.Function,), dict(forward=staticmethod(fwd), backward=staticmethod(bwd)))
+    return _NET_FUNCTIONS[key]
 
 
-def _dqn_evaluate_function():
-    """the torch.autograd.Function behind dqn_evaluate_torch"""
-    global _DQN_EVALUATE
-    if _DQN_EVALUATE is not None:
-        return _DQN_EVALUATE
+def _actor_critic_backward(grad_torch, skip):
+    """the backward of policy_evaluate_torch / population_evaluate_torch over env.<grad_torch>; skip: no call when no output was used
+    or no parameter needs a gradient"""
+    def backward(env, handle, obs, action, needs, g_logp, g_entropy, g_value=None):
+        if skip and ((g_logp is None and g_entropy is None and g_value is None) or not any(needs[1:])):
+            return None
+        out = getattr(env, grad_torch)(handle, obs, action, g_logp, g_entropy, g_value if handle.has_critic else None)
+        return (None, *_flat_grads(handle, out))
+    return backward
+
+
+def _q_backward(env, q, obs, action, needs, g_q1, g_q2=None):
+    want_params, want_action = any(needs[1:]), needs[0]
+    out = env.q_grad_torch(q, obs, action, g_q1, g_q2 if q.n_critics == 2 else None, params=want_params, action_grad=want_action)
+    return (out["action"], *_flat_grads(q, out))
+
+
+def _policy_action_backward(env, policy, obs, eps, needs, g_action):
+    if g_action is None or not any(needs[1:]):
+        return None
+    return (None, *_flat_grads(policy, env.policy_action_grad_torch(policy, obs, g_action, eps)))
+
+
+def _squashed_backward(env, sp, obs, eps, needs, g_action, g_logp):
+    if (g_action is None and g_logp is None) or not any(needs[1:]):
+        return None
+    return (None, *_flat_grads(sp, env.squashed_grad_torch(sp, obs, eps, g_action, g_logp)))
+
+
+def _dqn_forward(env, dqn, obs, action):
     import torch
-
-    class DqnEvaluate(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, dqn, obs, action, *params):
-            ctx.env, ctx.dqn, ctx.has_action = env, dqn, action is not None
-            ctx.save_for_backward(*((obs, action) if action is not None else (obs,)))
-            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
-            n = int(obs.shape[0])
-            out = dict(q_all=torch.empty((n, 6), dtype=torch.float32, device=obs.device))
-            if action is not None:
-                out["q_taken"] = torch.empty(n, dtype=torch.float32, device=obs.device)
-            q_all, q_taken = env.dqn_evaluate_raw_torch(dqn, obs, action, out=out)[:2]
-            return q_all if action is None else (q_all, q_taken)
-
-        @staticmethod
-        def backward(ctx, g_all, g_taken=None):
-            env, dqn = ctx.env, ctx.dqn
-            none = (None,) * (4 + len(dqn.tensors))
-            if (g_all is None and g_taken is None) or not any(ctx.needs_input_grad[4:]):
-                return none
-            obs = ctx.saved_tensors[0]
-            action = ctx.saved_tensors[1] if ctx.has_action and g_taken is not None else None
-            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            out = env.dqn_grad_torch(dqn, obs, action, con(g_taken), con(g_all))
-            return (None, None, None, None, *[t for pair in out["net"] for t in pair])
-
-    _DQN_EVALUATE = DqnEvaluate
-    return DqnEvaluate
+    n = int(obs.shape[0])
+    out = dict(q_all=torch.empty((n, 6), dtype=torch.float32, device=obs.device))
+    if action is not None:
+        out["q_taken"] = torch.empty(n, dtype=torch.float32, device=obs.device)
+    q_all, q_taken = env.dqn_evaluate_raw_torch(dqn, obs, action, out=out)[:2]
+    return q_all if action is None else (q_all, q_taken)
 
 
-def _squashed_sample_function():
-    """the torch.autograd.Function behind squashed_sample_torch"""
-    global _SQUASHED_SAMPLE
-    if _SQUASHED_SAMPLE is not None:
-        return _SQUASHED_SAMPLE
-    import torch
-
-    class SquashedSample(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, sp, obs, eps, *params):
-            ctx.env, ctx.sp, ctx.has_eps = env, sp, eps is not None
-            ctx.save_for_backward(*((obs, eps) if eps is not None else (obs,)))
-            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: a NULL g
-            return env.squashed_sample_raw_torch(sp, obs, eps)
-
-        @staticmethod
-        def backward(ctx, g_action, g_logp):
-            env, sp = ctx.env, ctx.sp
-            none = (None,) * (4 + len(sp.tensors))
-            if (g_action is None and g_logp is None) or not any(ctx.needs_input_grad[4:]):
-                return none
-            obs = ctx.saved_tensors[0]
-            eps = ctx.saved_tensors[1] if ctx.has_eps else None
-            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            out = env.squashed_grad_torch(sp, obs, eps, con(g_action), con(g_logp))
-            return (None, None, None, None, *[t for pair in out["actor"] for t in pair])
-
-    _SQUASHED_SAMPLE = SquashedSample
-    return SquashedSample
+def _dqn_backward(env, dqn, obs, action, needs, g_all, g_taken=None):
+    if (g_all is None and g_taken is None) or not any(needs[1:]):
+        return None
+    return (None, *_flat_grads(dqn, env.dqn_grad_torch(dqn, obs, action if g_taken is not None else None, g_taken, g_all)))
 
 
-def _q_evaluate_function():
-    """the torch.autograd.Function behind q_evaluate_torch (made on first use: torch is imported lazily)"""
-    global _Q_EVALUATE
-    if _Q_EVALUATE is not None:
-        return _Q_EVALUATE
-    import torch
-
-    class QEvaluate(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, q, obs, action, *params):
-            ctx.env, ctx.q = env, q
-            ctx.save_for_backward(obs, action)
-            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None: that critic is skipped
-            return env.q_evaluate_raw_torch(q, obs, action)
-
-        @staticmethod
-        def backward(ctx, g_q1, g_q2=None):
-            env, q = ctx.env, ctx.q
-            obs, action = ctx.saved_tensors
-            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            want_params, want_action = any(ctx.needs_input_grad[4:]), ctx.needs_input_grad[3]
-            out = env.q_grad_torch(q, obs, action, con(g_q1), con(g_q2) if q.n_critics == 2 else None, params=want_params,
-                                   action_grad=want_action)
-            L = q.n_hidden + 1
-            grads = [None] * (2 * L * q.n_critics)
-            if want_params:
-                grads = [t for pairs in out["critics"] for pair in pairs for t in pair]
-            return (None, None, None, out["action"], *grads)
-
-    _Q_EVALUATE = QEvaluate
-    return QEvaluate
-
-
-def _policy_action_function():
-    """the torch.autograd.Function behind policy_action_torch"""
-    global _POLICY_ACTION
-    if _POLICY_ACTION is not None:
-        return _POLICY_ACTION
-    import torch
-
-    class PolicyAction(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, policy, obs, eps, *params):
-            ctx.env, ctx.policy, ctx.has_eps = env, policy, eps is not None
-            ctx.save_for_backward(*((obs, eps) if eps is not None else (obs,)))
-            return env.policy_action_raw_torch(policy, obs, eps)
-
-        @staticmethod
-        def backward(ctx, g_action):
-            env, policy = ctx.env, ctx.policy
-            if g_action is None:
-                return (None,) * (4 + len(policy.tensors))
-            obs = ctx.saved_tensors[0]
-            eps = ctx.saved_tensors[1] if ctx.has_eps else None
-            L = policy.n_hidden + 1
-            none = [None] * (len(policy.tensors))
-            if not any(ctx.needs_input_grad[4:]):
-                return (None, None, None, None, *none)
-            out = env.policy_action_grad_torch(policy, obs, g_action.to(torch.float32).contiguous(), eps)
-            grads = [t for pair in out["actor"] for t in pair]
-            if policy.has_critic:
-                grads += [None] * (2 * L)
-            grads.append(out["log_std"])
-            return (None, None, None, None, *grads)
-
-    _POLICY_ACTION = PolicyAction
-    return PolicyAction
-
-
-def _policy_evaluate_function():
-    """the torch.autograd.Function behind policy_evaluate_torch (made on first use: torch is imported lazily)"""
-    global _POLICY_EVALUATE
-    if _POLICY_EVALUATE is not None:
-        return _POLICY_EVALUATE
-    import torch
-
-    class PolicyEvaluate(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, env, policy, obs, action, *params):
-            ctx.env, ctx.policy = env, policy
-            ctx.save_for_backward(obs, action)
-            logp, entropy, value = env.policy_evaluate_raw_torch(policy, obs, action)
-            if value is None:
-                return logp, entropy, None
-            return logp, entropy, value
-
-        @staticmethod
-        def backward(ctx, g_logp, g_entropy, g_value=None):
-            env, policy = ctx.env, ctx.policy
-            obs, action = ctx.saved_tensors
-            con = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            out = env.policy_grad_torch(policy, obs, action, con(g_logp), con(g_entropy), con(g_value) if policy.has_critic else None)
-            L = policy.n_hidden + 1
-            grads = [t for pair in out["actor"] for t in pair]
-            if policy.has_critic:
-                grads += [t for pair in out["critic"] for t in pair] if out["critic"] is not None else [None] * (2 * L)
-            if out["log_std"] is not None:
-                grads.append(out["log_std"])
-            return (None, None, None, None, *grads)
-
-    _POLICY_EVALUATE = PolicyEvaluate
-    return PolicyEvaluate
+# The methods that take or make a net handle: served by SpaceGymVectorEnv only, refused by the multi-device front ends
+NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "policy_evaluate_torch", "policy_evaluate_raw_torch", "policy_grad_torch",
+               "ppo_grad_torch", "ppo_assign_grads", "q_torch", "q_evaluate_torch", "q_evaluate_raw_torch", "q_grad_torch", "policy_action_torch",
+               "policy_action_raw_torch", "policy_action_grad_torch", "squashed_policy_torch", "squashed_act_torch", "rollout_squashed_torch",
+               "squashed_sample_torch", "squashed_sample_raw_torch", "squashed_grad_torch", "dqn_torch", "dqn_act_torch", "rollout_dqn_torch",
+               "dqn_evaluate_torch", "dqn_evaluate_raw_torch", "dqn_grad_torch", "policy_population_torch", "population_member_torch",
+               "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
+               "population_grad_torch")
 
 
 class SpaceGymVectorEnv:
@@ -1354,24 +1236,27 @@ class SpaceGymVectorEnv:
         return out["advantage"], out["returns"]
 
     # ------------------------------------------------------------------ what the net handles and their methods share
-    def _mlp_layers(self, name, layers, fan_in, out, mlp, keep):
+    def _mlp_layers(self, name, layers, fan_in, out, mlp, keep, members=None):
         """checks one net [(weight, bias), ...] of fan_in -> hidden -> ... -> out, writes its pointers into the sg_policy_mlp `mlp`,
-        appends its tensors to `keep` and returns (n_hidden, hidden)"""
+        appends its tensors to `keep` and returns (n_hidden, hidden); members: a stacked net (weight [P, width, fan_in], bias
+        [P, width]), whose pointers address member 0"""
         import torch
         layers = [tuple(l) for l in layers]
+        lead = () if members is None else (members,)
         n_hidden = len(layers) - 1
         if not 1 <= n_hidden <= 3:
             raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
         w0 = layers[0][0]
-        if not isinstance(w0, torch.Tensor) or w0.dim() != 2:
-            raise ValueError(f"{name}[0]: expected a weight of shape (hidden, {fan_in})")
-        hidden = int(w0.shape[0])
+        if not isinstance(w0, torch.Tensor) or w0.dim() != 2 + len(lead):
+            raise ValueError(f"{name}[0]: expected a " + (f"stacked weight of shape ({members}, hidden, {fan_in})" if lead else
+                                                          f"weight of shape (hidden, {fan_in})"))
+        hidden = int(w0.shape[-2])
         if not 1 <= hidden <= 128:
             raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
         for l, (w, b) in enumerate(layers):
             width = out if l == n_hidden else hidden
-            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (width, fan_in))
-            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (width,))
+            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (*lead, width, fan_in))
+            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (*lead, width))
             mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
             keep.extend((w, b))
             fan_in = hidden
@@ -1429,6 +1314,108 @@ class SpaceGymVectorEnv:
             ws = handle.workspace = torch.empty(need, dtype=torch.uint8, device=device)
         return ws
 
+    def _actor_critic_struct(self, members, actor, critic, log_std, activation):
+        """(the sg_policy over the nets of a policy, or over the stacked nets of `members` of them; the tensors it points into)"""
+        import torch
+        lead = () if members is None else (members,)
+        head = 6 if self.discrete else 2
+        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=_activation_code(activation), head=head)
+        keep = []
+        p.n_hidden, p.hidden = self._mlp_layers("actor", actor, self.obs_dim, head, p.actor, keep, members)
+        if critic is not None:
+            if self._mlp_layers("critic", critic, self.obs_dim, 1, p.critic, keep, members) != (p.n_hidden, p.hidden):
+                raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
+        if self.discrete:
+            if log_std is not None:
+                raise ValueError("log_std: the discrete ids take none")
+        else:
+            if log_std is None:
+                raise ValueError(f"log_std: a continuous id needs the float32 {list(lead + (2,))} log standard deviations")
+            self._check_tensor("log_std", log_std, torch.float32, (*lead, 2))
+            p.log_std = log_std.data_ptr()
+            keep.append(log_std)
+        return p, keep
+
+    def _act_out(self, out, noun, has_critic, device, values_alone):
+        """(action, logp, value) of an act call over the handle's envs: allocated, or out's, checked; values_alone: out may ask for
+        the values only"""
+        import torch
+        B = self.num_envs
+        a_dtype, a_shape = (torch.int32, (B,)) if self.discrete else (torch.float32, (B, 2))
+        if out is None:
+            return (torch.empty(a_shape, dtype=a_dtype, device=device), torch.empty(B, dtype=torch.float32, device=device),
+                    torch.empty(B, dtype=torch.float32, device=device) if has_critic else None)
+        action = logp = None
+        if not values_alone or out.get("action") is not None:
+            action, logp = out["action"], out["logp"]
+            self._check_tensor("out['action']", action, a_dtype, a_shape)
+            self._check_tensor("out['logp']", logp, torch.float32, (B,))
+        elif out.get("value") is None:
+            raise ValueError("out: expected action (with logp), value, or both")
+        value = out.get("value")
+        if value is not None:
+            if not has_critic:
+                raise ValueError(f"out['value']: the {noun} has no critic")
+            self._check_tensor("out['value']", value, torch.float32, (B,))
+        return action, logp, value
+
+    def _rollout_buffers(self, obs, action, action_like, cols, reward, done, trunc):
+        """checks the buffers of K closed-loop steps and returns K: obs [K + 1, B, D], action (action_like: the test of its dim() and
+        the shape the message names), then cols -- (name, float32 tensor, rows beyond K) -- and reward / done / trunc [K, B]"""
+        import torch
+        dim_ok, shape = action_like
+        if not isinstance(action, torch.Tensor) or not dim_ok(action.dim()) or int(action.shape[0]) < 1:
+            raise ValueError(f"action: expected a CUDA tensor {shape}of at least one step")
+        K, B = int(action.shape[0]), self.num_envs
+        self._check_tensor("obs", obs, torch.float32, (K + 1, B, self.obs_dim))
+        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
+        for name, t, extra in cols:
+            self._check_tensor(name, t, torch.float32, (K + extra, B))
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        return K
+
+    def _out_columns(self, out, cols):
+        """an out dict of optional columns, each (name, dtype, shape): at least one given, those given checked; returns them in
+        order, None for a column that is absent"""
+        if all(out.get(k) is None for k, _, _ in cols):
+            raise ValueError(f"out: expected at least one of {', '.join(k for k, _, _ in cols)}")
+        for k, dtype, shape in cols:
+            if out.get(k) is not None:
+                self._check_tensor(f"out['{k}']", out[k], dtype, shape)
+        return tuple(out.get(k) for k, _, _ in cols)
+
+    def _policy_grads(self, handle, out, noun, critic_needed, why):
+        """(out, its sg_policy_grads) for the gradients of a Policy or PolicyPopulation: out a dict actor / critic / log_std of tensors
+        like the parameters, made when None -- the critic's when critic_needed, else they may be absent (why: what the error says when
+        they are needed and are not there)"""
+        import torch
+        L = handle.n_hidden + 1
+        params = handle.tensors
+        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if handle.has_critic else ()
+        if out is None:
+            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if critic_needed else None,
+                       log_std=None if self.discrete else torch.empty_like(params[-1]))
+        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
+        if out.get("critic") is not None:
+            if not handle.has_critic:
+                raise ValueError(f"out['critic']: the {noun} has no critic")
+            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
+        elif critic_needed:
+            raise ValueError(f"out['critic']: {why}")
+        if self.discrete:
+            if out.get("log_std") is not None:
+                raise ValueError("out['log_std']: the discrete ids have none")
+        else:
+            shape = tuple(params[-1].shape)
+            if out.get("log_std") is None:
+                raise ValueError(f"out['log_std']: expected a float32 {list(shape)} tensor")
+            self._check_tensor("out['log_std']", out["log_std"], torch.float32, shape)
+            g.log_std = out["log_std"].data_ptr()
+        return out, g
+
     # ------------------------------------------------------------------ actor-critic policy on the device, closed-loop rollouts
     def policy_torch(self, actor, critic=None, log_std=None, activation="tanh"):
         """A handle on a small MLP actor-critic whose parameters stay where they are (sg_policy: no copy, no transpose; what an
@@ -1437,23 +1424,7 @@ class SpaceGymVectorEnv:
         (continuous ids: the mean; log_std float32 [2] is needed) or 6 (discrete ids: the logits), the critic -> 1 (None: no
         values).  Parameters of nn.Linear modules pass as they are: [(m.weight, m.bias) for m in linears].  activation: "tanh" or
         "relu", after every hidden layer."""
-        import torch
-        head = 6 if self.discrete else 2
-        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=_activation_code(activation), head=head)
-        keep = []
-        p.n_hidden, p.hidden = self._mlp_layers("actor", actor, self.obs_dim, head, p.actor, keep)
-        if critic is not None:
-            if self._mlp_layers("critic", critic, self.obs_dim, 1, p.critic, keep) != (p.n_hidden, p.hidden):
-                raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
-        if self.discrete:
-            if log_std is not None:
-                raise ValueError("log_std: the discrete ids take none")
-        else:
-            if log_std is None:
-                raise ValueError("log_std: a continuous id needs the float32 [2] log standard deviations")
-            self._check_tensor("log_std", log_std, torch.float32, (2,))
-            p.log_std = log_std.data_ptr()
-            keep.append(log_std)
+        p, keep = self._actor_critic_struct(None, actor, critic, log_std, activation)
         return Policy(p, keep, critic is not None)
 
     def policy_act_torch(self, policy, obs, seed=0, step=0, deterministic=False, out=None):
@@ -1464,27 +1435,18 @@ class SpaceGymVectorEnv:
         out: dict action / logp / value of tensors to fill (allocated when absent)."""
         import torch
         self._net_handle(policy, Policy)
-        B, D = self.num_envs, self.obs_dim
-        self._check_tensor("obs", obs, torch.float32, (B, D))
-        if out is None:
-            out = dict(action=torch.empty((B,) if self.discrete else (B, 2), dtype=torch.int32 if self.discrete else torch.float32, device=obs.device),
-                       logp=torch.empty(B, dtype=torch.float32, device=obs.device),
-                       value=torch.empty(B, dtype=torch.float32, device=obs.device) if policy.has_critic else None)
-        else:
-            self._check_tensor("out['action']", out["action"], torch.int32 if self.discrete else torch.float32, (B,) if self.discrete else (B, 2))
-            self._check_tensor("out['logp']", out["logp"], torch.float32, (B,))
-            if out.get("value") is not None:
-                if not policy.has_critic:
-                    raise ValueError("out['value']: the policy has no critic")
-                self._check_tensor("out['value']", out["value"], torch.float32, (B,))
-        value = out.get("value")
+        self._check_tensor("obs", obs, torch.float32, (self.num_envs, self.obs_dim))
+        action, logp, value = self._act_out(out, "policy", policy.has_critic, obs.device, values_alone=False)
         self._ck(self._lib.sg_policy_act_device(self._h, C.byref(policy.struct), _ptr(obs), int(seed), int(step), int(bool(deterministic)),
-                                                _ptr(out["action"]), _ptr(out["logp"]), _ptr(value), self._stream()), "sg_policy_act_device")
-        return out["action"], out["logp"], value
+                                                _ptr(action), _ptr(logp), _ptr(value), self._stream()), "sg_policy_act_device")
+        return action, logp, value
 
     def _terminal_list_struct(self, terminal):
-        """checks a terminal_list_torch dict and returns (its sg_terminal_list, its capacity): shared by the closed-loop rollouts"""
+        """checks a terminal_list_torch dict and returns (its sg_terminal_list by reference, its capacity), (None, None) for None: shared
+        by the closed-loop rollouts"""
         import torch
+        if terminal is None:
+            return None, None
         for k in ("count", "step_env", "obs"):
             if not isinstance(terminal.get(k), torch.Tensor):
                 raise ValueError(f"terminal['{k}']: expected a CUDA tensor (terminal_list_torch makes the dict)")
@@ -1496,7 +1458,7 @@ class SpaceGymVectorEnv:
         self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
         self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
         self._check_tensor("terminal['obs']", terminal["obs"], torch.float32, (cap, self.obs_dim))
-        return _native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap), cap
+        return C.byref(_native.SgTerminalList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["obs"].data_ptr(), cap)), cap
 
     def rollout_policy_torch(self, policy, obs, action, logp, value, reward, done, trunc, seed=0, first_step=0, deterministic=False,
                              terminal=None):
@@ -1510,33 +1472,22 @@ class SpaceGymVectorEnv:
         needs nothing in between."""
         import torch
         self._net_handle(policy, Policy)
-        if not isinstance(action, torch.Tensor) or action.dim() < 2 or int(action.shape[0]) < 1:
-            raise ValueError("action: expected a CUDA tensor of at least one step")
-        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
         if policy.has_critic and value is None:
             raise ValueError("value: the policy has a critic; pass the float32 [K + 1, B] tensor its values go to")
         if not policy.has_critic and value is not None:
             raise ValueError("value: the policy has no critic")
-        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
-        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
-        self._check_tensor("logp", logp, torch.float32, (K, B))
-        if value is not None:
-            self._check_tensor("value", value, torch.float32, (K + 1, B))
-        self._check_tensor("reward", reward, torch.float32, (K, B))
-        self._check_tensor("done", done, torch.uint8, (K, B))
-        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
-        tl, tv = None, None
-        if terminal is not None:
-            tl, cap = self._terminal_list_struct(terminal)
-            if policy.has_critic:
-                if terminal.get("value") is None:
-                    terminal["value"] = torch.empty(cap, dtype=torch.float32, device=terminal["obs"].device)
-                self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
-                tv = terminal["value"]
+        K = self._rollout_buffers(obs, action, (lambda d: d >= 2, ""), [("logp", logp, 0)] + [("value", value, 1)] * (value is not None), reward,
+                                  done, trunc)
+        tl, cap = self._terminal_list_struct(terminal)
+        tv = None
+        if terminal is not None and policy.has_critic:
+            if terminal.get("value") is None:
+                terminal["value"] = torch.empty(cap, dtype=torch.float32, device=terminal["obs"].device)
+            self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
+            tv = terminal["value"]
         self._ck(self._lib.sg_rollout_policy_device(self._h, K, C.byref(policy.struct), int(seed), int(first_step), int(bool(deterministic)),
                                                     _ptr(obs), _ptr(action), _ptr(logp), _ptr(value), _ptr(reward), _ptr(done), _ptr(trunc),
-                                                    C.byref(tl) if tl is not None else None, _ptr(tv), self._stream()),
-                 "sg_rollout_policy_device")
+                                                    tl, _ptr(tv), self._stream()), "sg_rollout_policy_device")
         return obs, action, logp, value, reward, done, trunc
 
     # ------------------------------------------------------------------ the learner's half: evaluate given actions, parameter gradients
@@ -1550,17 +1501,12 @@ class SpaceGymVectorEnv:
         n = self._net_rows(policy, Policy, obs, action=action)
         if out is None:
             out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in (("logp", "entropy", "value") if policy.has_critic else ("logp", "entropy"))}
-        else:
-            if out.get("value") is not None and not policy.has_critic:
-                raise ValueError("out['value']: the policy has no critic")
-            if all(out.get(k) is None for k in ("logp", "entropy", "value")):
-                raise ValueError("out: expected at least one of logp, entropy, value")
-            for k in ("logp", "entropy", "value"):
-                if out.get(k) is not None:
-                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
-        self._ck(self._lib.sg_policy_evaluate_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("logp")),
-                                                     _ptr(out.get("entropy")), _ptr(out.get("value")), self._stream()), "sg_policy_evaluate_device")
-        return out.get("logp"), out.get("entropy"), out.get("value")
+        elif out.get("value") is not None and not policy.has_critic:
+            raise ValueError("out['value']: the policy has no critic")
+        cols = self._out_columns(out, [(k, torch.float32, (n,)) for k in ("logp", "entropy", "value")])
+        self._ck(self._lib.sg_policy_evaluate_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(action), *map(_ptr, cols), self._stream()),
+                 "sg_policy_evaluate_device")
+        return cols
 
     def policy_grad_torch(self, policy, obs, action, g_logp=None, g_entropy=None, g_value=None, out=None):
         """Gradients of a loss with respect to the policy's parameters, given the loss's gradients g_logp / g_entropy / g_value
@@ -1576,28 +1522,7 @@ class SpaceGymVectorEnv:
                 self._check_tensor(name, g, torch.float32, (n,))
         if g_value is not None and not policy.has_critic:
             raise ValueError("g_value: the policy has no critic")
-        L = policy.n_hidden + 1
-        params = policy.tensors
-        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if policy.has_critic else ()
-        if out is None:
-            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if g_value is not None else None,
-                       log_std=None if self.discrete else torch.empty_like(params[-1]))
-        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
-        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
-        if out.get("critic") is not None:
-            if not policy.has_critic:
-                raise ValueError("out['critic']: the policy has no critic")
-            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
-        elif g_value is not None:
-            raise ValueError("out['critic']: g_value is given; the critic's gradients need tensors")
-        if self.discrete:
-            if out.get("log_std") is not None:
-                raise ValueError("out['log_std']: the discrete ids have none")
-        else:
-            if out.get("log_std") is None:
-                raise ValueError("out['log_std']: expected a float32 [2] tensor")
-            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
-            g.log_std = out["log_std"].data_ptr()
+        out, g = self._policy_grads(policy, out, "policy", g_value is not None, "g_value is given; the critic's gradients need tensors")
         ws = self._grad_workspace(policy, "sg_policy_grad_workspace_bytes", n, obs.device, "policy_grad_torch", "sg_policy_grad_workspace_bytes")
         self._ck(self._lib.sg_policy_grad_device(self._h, C.byref(policy.struct), n, _ptr(obs), _ptr(action), _ptr(g_logp), _ptr(g_entropy),
                                                  _ptr(g_value), C.byref(g), _ptr(ws), ws.numel(), self._stream()), "sg_policy_grad_device")
@@ -1610,7 +1535,8 @@ class SpaceGymVectorEnv:
         the loss in torch on the three [n] vectors and call backward(): the parameters' .grad accumulate as usual.  Under
         torch.no_grad(), or when no parameter requires grad, it is the plain forward.  value is None without a critic."""
         self._net_rows(policy, Policy, obs, action=action)
-        return _policy_evaluate_function().apply(self, policy, obs, action, *policy.tensors)
+        fn = _net_function("PolicyEvaluate", lambda env, h, o, a: env.policy_evaluate_raw_torch(h, o, a), _actor_critic_backward("policy_grad_torch", False), True)
+        return fn.apply(self, policy, obs, action, *policy.tensors)
 
     # ------------------------------------------------------------------ the PPO minibatch update: loss, statistics and gradients in one call
     ppo_stats_names = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "old_approx_kl", "clip_fraction", "adv_mean", "adv_std",
@@ -1661,28 +1587,7 @@ class SpaceGymVectorEnv:
             self._check_tensor("index", index, torch.int64, (n,))
         if normalize_advantage and n < 2:
             raise ValueError("normalize_advantage: needs n >= 2")
-        L = policy.n_hidden + 1
-        params = policy.tensors
-        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if policy.has_critic else ()
-        if out is None:
-            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if policy.has_critic else None,
-                       log_std=None if self.discrete else torch.empty_like(params[-1]))
-        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
-        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
-        if policy.has_critic:
-            if out.get("critic") is None:
-                raise ValueError("out['critic']: the policy has a critic; its gradients need tensors")
-            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
-        elif out.get("critic") is not None:
-            raise ValueError("out['critic']: the policy has no critic")
-        if self.discrete:
-            if out.get("log_std") is not None:
-                raise ValueError("out['log_std']: the discrete ids have none")
-        else:
-            if out.get("log_std") is None:
-                raise ValueError("out['log_std']: expected a float32 [2] tensor")
-            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
-            g.log_std = out["log_std"].data_ptr()
+        out, g = self._policy_grads(policy, out, "policy", policy.has_critic, "the policy has a critic; its gradients need tensors")
         if stats is None:
             stats = obs.new_empty(len(self.ppo_stats_names))
         else:
@@ -1715,40 +1620,11 @@ class SpaceGymVectorEnv:
     def ppo_assign_grads(policy, grads):
         """makes ppo_grad_torch's (or policy_grad_torch's) tensors the .grad of the parameters the handle holds, so that optimizer.step()
         follows directly; a net whose gradients are None keeps its .grad"""
-        L = policy.n_hidden + 1
-        params = policy.tensors
-        flat = [t for pair in grads["actor"] for t in pair]
-        if policy.has_critic:
-            flat += [t for pair in grads["critic"] for t in pair] if grads.get("critic") is not None else [None] * (2 * L)
-        if grads.get("log_std") is not None:
-            flat.append(grads["log_std"])
-        for p, t in zip(params, flat):
+        for p, t in zip(policy.tensors, _flat_grads(policy, grads)):
             if t is not None:
                 p.grad = t
 
     # ------------------------------------------------------------------ policy populations: P stacked actor-critics on P env blocks per launch
-    def _stacked_layers(self, name, layers, members, fan_in, out, mlp, keep):
-        """_mlp_layers for one stacked net [(weight [P, width, fan_in], bias [P, width]), ...]: the pointers address member 0"""
-        import torch
-        layers = [tuple(l) for l in layers]
-        n_hidden = len(layers) - 1
-        if not 1 <= n_hidden <= 3:
-            raise ValueError(f"{name}: n_hidden must be 1 .. 3 (2 .. 4 (weight, bias) pairs with the head), got {n_hidden}")
-        w0 = layers[0][0]
-        if not isinstance(w0, torch.Tensor) or w0.dim() != 3:
-            raise ValueError(f"{name}[0]: expected a stacked weight of shape ({members}, hidden, {fan_in})")
-        hidden = int(w0.shape[1])
-        if not 1 <= hidden <= 128:
-            raise ValueError(f"{name}: hidden must be 1 .. 128, got {hidden}")
-        for l, (w, b) in enumerate(layers):
-            width = out if l == n_hidden else hidden
-            self._check_tensor(f"{name}[{l}] weight", w, torch.float32, (members, width, fan_in))
-            self._check_tensor(f"{name}[{l}] bias", b, torch.float32, (members, width))
-            mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
-            keep.extend((w, b))
-            fan_in = hidden
-        return n_hidden, hidden
-
     def _population(self, pop, per_env=False):
         """checks a policy_population_torch handle; per_env: its members must divide this handle's envs"""
         self._net_handle(pop, PolicyPopulation)
@@ -1763,28 +1639,12 @@ class SpaceGymVectorEnv:
         float32 [P, 2] (continuous ids).  Member m owns the contiguous env block [m B / P, (m + 1) B / P) of the handle's B envs in
         population_act_torch / rollout_population_torch (P must divide B) and rows [m] of the [P, n, ...] tensors of the evaluate
         and grad calls.  A PBT exploit step is W[loser].copy_(W[winner]) on the caller's tensors: the next call reads it."""
-        import torch
         members = int(members)
         if not 1 <= members <= 65535:
             raise ValueError(f"members must be 1 .. 65535, got {members}")
         if self.num_envs % members:
             raise ValueError(f"members: {members} does not divide num_envs = {self.num_envs}")
-        head = 6 if self.discrete else 2
-        p = _native.SgPolicy(struct_size=C.sizeof(_native.SgPolicy), activation=_activation_code(activation), head=head)
-        keep = []
-        p.n_hidden, p.hidden = self._stacked_layers("actor", actor, members, self.obs_dim, head, p.actor, keep)
-        if critic is not None:
-            if self._stacked_layers("critic", critic, members, self.obs_dim, 1, p.critic, keep) != (p.n_hidden, p.hidden):
-                raise ValueError(f"critic: expected {p.n_hidden} hidden layers of width {p.hidden}, like the actor")
-        if self.discrete:
-            if log_std is not None:
-                raise ValueError("log_std: the discrete ids take none")
-        else:
-            if log_std is None:
-                raise ValueError(f"log_std: a continuous id needs the float32 [{members}, 2] log standard deviations")
-            self._check_tensor("log_std", log_std, torch.float32, (members, 2))
-            p.log_std = log_std.data_ptr()
-            keep.append(log_std)
+        p, keep = self._actor_critic_struct(members, actor, critic, log_std, activation)
         return PolicyPopulation(p, keep, critic is not None, members)
 
     def population_member_torch(self, pop, m):
@@ -1805,24 +1665,8 @@ class SpaceGymVectorEnv:
         graph-capturable): the same tensors, and per row bit for bit what policy_act_torch gives with that member's handle."""
         import torch
         self._population(pop, per_env=True)
-        B, D = self.num_envs, self.obs_dim
-        self._check_tensor("obs", obs, torch.float32, (B, D))
-        if out is None:
-            out = dict(action=torch.empty((B,) if self.discrete else (B, 2), dtype=torch.int32 if self.discrete else torch.float32, device=obs.device),
-                       logp=torch.empty(B, dtype=torch.float32, device=obs.device),
-                       value=torch.empty(B, dtype=torch.float32, device=obs.device) if pop.has_critic else None)
-        else:
-            if out.get("action") is None and out.get("value") is None:
-                raise ValueError("out: expected action (with logp), value, or both")
-            if out.get("action") is not None:
-                self._check_tensor("out['action']", out["action"], torch.int32 if self.discrete else torch.float32, (B,) if self.discrete else (B, 2))
-                self._check_tensor("out['logp']", out["logp"], torch.float32, (B,))
-            if out.get("value") is not None:
-                if not pop.has_critic:
-                    raise ValueError("out['value']: the population has no critic")
-                self._check_tensor("out['value']", out["value"], torch.float32, (B,))
-        action, value = out.get("action"), out.get("value")
-        logp = out.get("logp") if action is not None else None
+        self._check_tensor("obs", obs, torch.float32, (self.num_envs, self.obs_dim))
+        action, logp, value = self._act_out(out, "population", pop.has_critic, obs.device, values_alone=True)
         self._ck(self._lib.sg_policy_population_act_device(self._h, C.byref(pop.struct), pop.members, _ptr(obs), int(seed), int(step),
                                                            int(bool(deterministic)), _ptr(action), _ptr(logp), _ptr(value), self._stream()),
                  "sg_policy_population_act_device")
@@ -1838,27 +1682,17 @@ class SpaceGymVectorEnv:
             env.gae_torch(reward, done, trunc, value[:-1], value[-1], terminal_value=terminal_value)"""
         import torch
         self._population(pop, per_env=True)
-        if not isinstance(action, torch.Tensor) or action.dim() < 2 or int(action.shape[0]) < 1:
-            raise ValueError("action: expected a CUDA tensor of at least one step")
-        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
         if pop.has_critic and value is None:
             raise ValueError("value: the population has a critic; pass the float32 [K + 1, B] tensor its values go to")
         if not pop.has_critic and (value is not None or terminal_value is not None):
             raise ValueError("value / terminal_value: the population has no critic")
-        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
-        self._check_tensor("action", action, torch.int32 if self.discrete else torch.float32, (K, B) if self.discrete else (K, B, 2))
-        self._check_tensor("logp", logp, torch.float32, (K, B))
-        if value is not None:
-            self._check_tensor("value", value, torch.float32, (K + 1, B))
-        self._check_tensor("reward", reward, torch.float32, (K, B))
-        self._check_tensor("done", done, torch.uint8, (K, B))
-        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        K = self._rollout_buffers(obs, action, (lambda d: d >= 2, ""), [("logp", logp, 0)] + [("value", value, 1)] * (value is not None), reward,
+                                  done, trunc)
         if terminal_value is not None:
-            self._check_tensor("terminal_value", terminal_value, torch.float32, (K, B))
-        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
+            self._check_tensor("terminal_value", terminal_value, torch.float32, (K, self.num_envs))
         self._ck(self._lib.sg_rollout_policy_population_device(
             self._h, K, C.byref(pop.struct), pop.members, int(seed), int(first_step), int(bool(deterministic)), _ptr(obs), _ptr(action),
-            _ptr(logp), _ptr(value), _ptr(reward), _ptr(done), _ptr(trunc), C.byref(tl) if tl is not None else None, _ptr(terminal_value),
+            _ptr(logp), _ptr(value), _ptr(reward), _ptr(done), _ptr(trunc), self._terminal_list_struct(terminal)[0], _ptr(terminal_value),
             self._stream()), "sg_rollout_policy_population_device")
         return obs, action, logp, value, reward, done, trunc
 
@@ -1881,18 +1715,12 @@ class SpaceGymVectorEnv:
         P, n = self._population_rows(pop, obs, action)
         if out is None:
             out = {k: torch.empty((P, n), dtype=torch.float32, device=obs.device) for k in (("logp", "entropy", "value") if pop.has_critic else ("logp", "entropy"))}
-        else:
-            if out.get("value") is not None and not pop.has_critic:
-                raise ValueError("out['value']: the population has no critic")
-            if all(out.get(k) is None for k in ("logp", "entropy", "value")):
-                raise ValueError("out: expected at least one of logp, entropy, value")
-            for k in ("logp", "entropy", "value"):
-                if out.get(k) is not None:
-                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (P, n))
-        self._ck(self._lib.sg_policy_population_evaluate_device(self._h, C.byref(pop.struct), P, n, _ptr(obs), _ptr(action), _ptr(out.get("logp")),
-                                                                _ptr(out.get("entropy")), _ptr(out.get("value")), self._stream()),
-                 "sg_policy_population_evaluate_device")
-        return out.get("logp"), out.get("entropy"), out.get("value")
+        elif out.get("value") is not None and not pop.has_critic:
+            raise ValueError("out['value']: the population has no critic")
+        cols = self._out_columns(out, [(k, torch.float32, (P, n)) for k in ("logp", "entropy", "value")])
+        self._ck(self._lib.sg_policy_population_evaluate_device(self._h, C.byref(pop.struct), P, n, _ptr(obs), _ptr(action), *map(_ptr, cols),
+                                                                self._stream()), "sg_policy_population_evaluate_device")
+        return cols
 
     def population_grad_torch(self, pop, obs, action, g_logp=None, g_entropy=None, g_value=None, out=None):
         """policy_grad_torch for every member on its own n rows (sg_policy_population_grad_device: two launches, graph-capturable
@@ -1907,28 +1735,7 @@ class SpaceGymVectorEnv:
                 self._check_tensor(name, g, torch.float32, (P, n))
         if g_value is not None and not pop.has_critic:
             raise ValueError("g_value: the population has no critic")
-        L = pop.n_hidden + 1
-        params = pop.tensors
-        a_par, c_par = params[:2 * L], params[2 * L:4 * L] if pop.has_critic else ()
-        if out is None:
-            out = dict(actor=_empty_pairs(a_par), critic=_empty_pairs(c_par) if g_value is not None else None,
-                       log_std=None if self.discrete else torch.empty_like(params[-1]))
-        g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
-        self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
-        if out.get("critic") is not None:
-            if not pop.has_critic:
-                raise ValueError("out['critic']: the population has no critic")
-            self._grad_pairs("out['critic']", out["critic"], c_par, g.critic)
-        elif g_value is not None:
-            raise ValueError("out['critic']: g_value is given; the critic's gradients need tensors")
-        if self.discrete:
-            if out.get("log_std") is not None:
-                raise ValueError("out['log_std']: the discrete ids have none")
-        else:
-            if out.get("log_std") is None:
-                raise ValueError(f"out['log_std']: expected a float32 [{P}, 2] tensor")
-            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (P, 2))
-            g.log_std = out["log_std"].data_ptr()
+        out, g = self._policy_grads(pop, out, "population", g_value is not None, "g_value is given; the critic's gradients need tensors")
         ws = self._grad_workspace(pop, "sg_policy_population_grad_workspace_bytes", n, obs.device, "population_grad_torch",
                                   "sg_policy_population_grad_workspace_bytes", members=P)
         self._ck(self._lib.sg_policy_population_grad_device(self._h, C.byref(pop.struct), P, n, _ptr(obs), _ptr(action), _ptr(g_logp), _ptr(g_entropy),
@@ -1942,7 +1749,8 @@ class SpaceGymVectorEnv:
         population_grad_torch call (a None g for an output the loss did not use).  A loss summed over the members' losses gives every
         member its own gradient in its slices; .grad accumulates as usual.  value is None without a critic."""
         self._population_rows(pop, obs, action)
-        return _population_evaluate_function().apply(self, pop, obs, action, *pop.tensors)
+        fn = _net_function("PopulationEvaluate", lambda env, h, o, a: env.population_evaluate_raw_torch(h, o, a), _actor_critic_backward("population_grad_torch", True))
+        return fn.apply(self, pop, obs, action, *pop.tensors)
 
     # ------------------------------------------------------------------ the off-policy learner's nets: twin Q critics, action gradients
     def q_torch(self, critics, activation="relu"):
@@ -1973,17 +1781,12 @@ class SpaceGymVectorEnv:
         n = self._net_rows(q, QNet, obs, action=action)
         if out is None:
             out = {k: torch.empty(n, dtype=torch.float32, device=obs.device) for k in ("q1", "q2")[:q.n_critics]}
-        else:
-            if out.get("q2") is not None and q.n_critics != 2:
-                raise ValueError("out['q2']: the handle has one critic")
-            if out.get("q1") is None and out.get("q2") is None:
-                raise ValueError("out: expected at least one of q1, q2")
-            for k in ("q1", "q2"):
-                if out.get(k) is not None:
-                    self._check_tensor(f"out['{k}']", out[k], torch.float32, (n,))
-        self._ck(self._lib.sg_q_evaluate_device(self._h, C.byref(q.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("q1")), _ptr(out.get("q2")),
-                                                self._stream()), "sg_q_evaluate_device")
-        return out.get("q1"), out.get("q2")
+        elif out.get("q2") is not None and q.n_critics != 2:
+            raise ValueError("out['q2']: the handle has one critic")
+        q1, q2 = self._out_columns(out, [(k, torch.float32, (n,)) for k in ("q1", "q2")])
+        self._ck(self._lib.sg_q_evaluate_device(self._h, C.byref(q.struct), n, _ptr(obs), _ptr(action), _ptr(q1), _ptr(q2), self._stream()),
+                 "sg_q_evaluate_device")
+        return q1, q2
 
     def q_grad_torch(self, q, obs, action, g_q1=None, g_q2=None, params=True, action_grad=False, out=None):
         """The critics' half of a backward pass, given the loss's gradients g_q1 / g_q2 (float32 [n], None: zeros) by
@@ -2039,7 +1842,8 @@ class SpaceGymVectorEnv:
         no parameter needs a gradient, action_grad only when the action needs one.  q2 is None with one critic.  With
         policy_action_torch it makes a TD3 / DDPG update plain torch on [n] vectors."""
         self._net_rows(q, QNet, obs, action=action)
-        return _q_evaluate_function().apply(self, q, obs, action, *q.tensors)
+        fn = _net_function("QEvaluate", lambda env, h, o, a: env.q_evaluate_raw_torch(h, o, a), _q_backward)
+        return fn.apply(self, q, obs, action, *q.tensors)
 
     def policy_action_raw_torch(self, policy, obs, eps=None, out=None):
         """action float32 [n, 2] = mean(obs) + exp(log_std) * eps under a policy_torch handle of a continuous id, unclamped; eps
@@ -2083,7 +1887,8 @@ class SpaceGymVectorEnv:
         of the handle: a torch.autograd.Function over policy_action_raw_torch / policy_action_grad_torch.  obs and eps get None.  The
         action is unclamped; clamp it in torch where the algorithm wants that."""
         self._net_rows(policy, Policy, obs, "policy_action_torch", eps=eps)
-        return _policy_action_function().apply(self, policy, obs, eps, *policy.tensors)
+        fn = _net_function("PolicyAction", lambda env, h, o, e: env.policy_action_raw_torch(h, o, e), _policy_action_backward, True)
+        return fn.apply(self, policy, obs, eps, *policy.tensors)
 
     # ------------------------------------------------------------------ the SAC actor: tanh-squashed Gaussian, state-dependent log_std
     def squashed_policy_torch(self, actor, log_std_bounds=(-20.0, 2.0), activation="relu"):
@@ -2137,22 +1942,11 @@ class SpaceGymVectorEnv:
         step_torch would.  obs float32 [K + 1, B, D] with the current observations in row 0; action float32 [K, B, 2]; reward float32 /
         done, trunc uint8 [K, B]; logp float32 [K, B] or None.  terminal: a terminal_list_torch dict, filled like rollout_torch's.  The
         buffers may be a replay ring's rows(K)."""
-        import torch
         self._net_handle(sp, SquashedPolicy, "rollout_squashed_torch")
-        if not isinstance(action, torch.Tensor) or action.dim() != 3 or int(action.shape[0]) < 1:
-            raise ValueError("action: expected a CUDA tensor [K, B, 2] of at least one step")
-        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
-        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
-        self._check_tensor("action", action, torch.float32, (K, B, 2))
-        if logp is not None:
-            self._check_tensor("logp", logp, torch.float32, (K, B))
-        self._check_tensor("reward", reward, torch.float32, (K, B))
-        self._check_tensor("done", done, torch.uint8, (K, B))
-        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
-        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
+        K = self._rollout_buffers(obs, action, (lambda d: d == 3, "[K, B, 2] "), [("logp", logp, 0)] * (logp is not None), reward, done, trunc)
         self._ck(self._lib.sg_rollout_squashed_device(self._h, K, C.byref(sp.struct), int(seed), int(first_step), int(bool(deterministic)),
                                                       _ptr(obs), _ptr(action), _ptr(logp), _ptr(reward), _ptr(done), _ptr(trunc),
-                                                      C.byref(tl) if tl is not None else None, self._stream()), "sg_rollout_squashed_device")
+                                                      self._terminal_list_struct(terminal)[0], self._stream()), "sg_rollout_squashed_device")
         return obs, action, logp, reward, done, trunc
 
     def squashed_sample_raw_torch(self, sp, obs, eps=None, out=None):
@@ -2195,7 +1989,8 @@ class SpaceGymVectorEnv:
             a, lp = env.squashed_sample_torch(sp, obs, torch.randn_like(...))
             (alpha * lp - torch.min(*env.q_evaluate_torch(q, obs, a))).mean().backward()"""
         self._net_rows(sp, SquashedPolicy, obs, "squashed_sample_torch", eps=eps)
-        return _squashed_sample_function().apply(self, sp, obs, eps, *sp.tensors)
+        fn = _net_function("SquashedSample", lambda env, h, o, e: env.squashed_sample_raw_torch(h, o, e), _squashed_backward)
+        return fn.apply(self, sp, obs, eps, *sp.tensors)
 
     # ------------------------------------------------------------------ the DQN head of the discrete ids: Q(obs) -> 6, epsilon-greedy
     def _dqn_handle(self, dqn, who):
@@ -2265,23 +2060,12 @@ class SpaceGymVectorEnv:
         dqn_act_torch followed by step_torch would.  obs float32 [K + 1, B, D] with the current observations in row 0; action int32
         [K, B]; reward float32 / done, trunc uint8 [K, B]; q float32 [K, B] or None.  terminal: a terminal_list_torch dict, filled
         like rollout_torch's.  The buffers may be a replay ring's rows(K)."""
-        import torch
         self._dqn_handle(dqn, "rollout_dqn_torch")
-        if not isinstance(action, torch.Tensor) or action.dim() != 2 or int(action.shape[0]) < 1:
-            raise ValueError("action: expected a CUDA tensor [K, B] of at least one step")
-        K, B, D = int(action.shape[0]), self.num_envs, self.obs_dim
-        self._check_tensor("obs", obs, torch.float32, (K + 1, B, D))
-        self._check_tensor("action", action, torch.int32, (K, B))
-        if q is not None:
-            self._check_tensor("q", q, torch.float32, (K, B))
-        self._check_tensor("reward", reward, torch.float32, (K, B))
-        self._check_tensor("done", done, torch.uint8, (K, B))
-        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        K = self._rollout_buffers(obs, action, (lambda d: d == 2, "[K, B] "), [("q", q, 0)] * (q is not None), reward, done, trunc)
         eps, eps_dev = self._dqn_epsilon(epsilon)
-        tl = self._terminal_list_struct(terminal)[0] if terminal is not None else None
         self._ck(self._lib.sg_rollout_dqn_device(self._h, K, C.byref(dqn.struct), int(seed), int(first_step), eps, _ptr(eps_dev), _ptr(obs),
                                                  _ptr(action), _ptr(q), _ptr(reward), _ptr(done), _ptr(trunc),
-                                                 C.byref(tl) if tl is not None else None, self._stream()), "sg_rollout_dqn_device")
+                                                 self._terminal_list_struct(terminal)[0], self._stream()), "sg_rollout_dqn_device")
         return obs, action, q, reward, done, trunc
 
     def dqn_evaluate_raw_torch(self, dqn, obs, action=None, out=None):
@@ -2297,19 +2081,13 @@ class SpaceGymVectorEnv:
         if out is None:
             out = dict(q_all=f32(n, 6), q_taken=f32(n) if action is not None else None, q_max=f32(n),
                        argmax=torch.empty(n, dtype=torch.int32, device=obs.device))
-        else:
-            if all(out.get(k) is None for k in ("q_all", "q_taken", "q_max", "argmax")):
-                raise ValueError("out: expected at least one of q_all, q_taken, q_max, argmax")
-            if out.get("q_taken") is not None and action is None:
-                raise ValueError("action: out['q_taken'] is given; expected the int32 [n] actions")
-            for k, dtype, shape in (("q_all", torch.float32, (n, 6)), ("q_taken", torch.float32, (n,)), ("q_max", torch.float32, (n,)),
-                                    ("argmax", torch.int32, (n,))):
-                if out.get(k) is not None:
-                    self._check_tensor(f"out['{k}']", out[k], dtype, shape)
-        self._ck(self._lib.sg_dqn_evaluate_device(self._h, C.byref(dqn.struct), n, _ptr(obs), _ptr(action), _ptr(out.get("q_all")),
-                                                  _ptr(out.get("q_taken")), _ptr(out.get("q_max")), _ptr(out.get("argmax")), self._stream()),
+        elif out.get("q_taken") is not None and action is None:
+            raise ValueError("action: out['q_taken'] is given; expected the int32 [n] actions")
+        cols = self._out_columns(out, [("q_all", torch.float32, (n, 6)), ("q_taken", torch.float32, (n,)), ("q_max", torch.float32, (n,)),
+                                       ("argmax", torch.int32, (n,))])
+        self._ck(self._lib.sg_dqn_evaluate_device(self._h, C.byref(dqn.struct), n, _ptr(obs), _ptr(action), *map(_ptr, cols), self._stream()),
                  "sg_dqn_evaluate_device")
-        return out.get("q_all"), out.get("q_taken"), out.get("q_max"), out.get("argmax")
+        return cols
 
     def dqn_grad_torch(self, dqn, obs, action=None, g_taken=None, g_all=None, out=None):
         """Gradients of a loss with respect to the net's parameters, given the loss's gradients g_taken float32 [n] and g_all float32
@@ -2347,7 +2125,7 @@ class SpaceGymVectorEnv:
                 target = reward + discount * env.dqn_evaluate_raw_torch(target_net, next_obs, a2)[1]
             huber(env.dqn_evaluate_torch(online, obs, action)[1], target).mean().backward()"""
         self._dqn_rows(dqn, "dqn_evaluate_torch", obs, action)
-        return _dqn_evaluate_function().apply(self, dqn, obs, action, *dqn.tensors)
+        return _net_function("DqnEvaluate", _dqn_forward, _dqn_backward).apply(self, dqn, obs, action, *dqn.tensors)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

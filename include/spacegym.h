@@ -960,6 +960,43 @@ int sg_policy_population_grad_device(sg_env *env, const sg_policy *policy, int32
 /* Bytes of workspace sg_policy_population_grad_device needs for n rows per member; 0 and an error message for an invalid policy, members or n */
 size_t sg_policy_population_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int32_t members, int64_t n);
 
+/* sg_ppo_grad_device for `members` members in one call: population-based training's update.  policy and grads are the stacked structs of
+ * the population calls above; cfg, batch and row_out are sg_ppo_grad_device's structs, unchanged in size.
+ * batch is ONE flattened rollout of `rows` rows shared by all members -- the six columns as there; the [K, num_envs] buffers of
+ * sg_rollout_policy_population_device and sg_gae_device serve reshaped, without a permuting copy.  batch.index is int64 [members, n]:
+ * entry (m, i) is the row member m's minibatch entry i reads, so the gather is what puts a member's env block into its minibatch;
+ * repeats are allowed and nothing checks that a row "belongs" to the member.  A NULL index gives member m the rows [m n, (m + 1) n),
+ * which needs members x n <= rows.  An index outside [0, rows) is handled as there: clamped before any address is formed from it, zero
+ * in every gradient and statistic, counted in THAT member's bad_rows.
+ * Per member: the advantage mean and std (float64, unbiased) over member m's n entries; the clipped objective and the subgradients
+ * exactly sg_ppo_grad_device's; stats_out float32 [members, 12]; the gradients WRITTEN into slice m of the stacked tensors; row_out's
+ * vectors float32 [members, n].
+ * member_coef (may be NULL): float32 DEVICE [members, 4], row m = (clip_range, clip_range_vf, ent_coef, vf_coef) of member m.  Given, it
+ * replaces those four members of cfg for every member and is read by the kernels at every launch, so a captured graph changes the
+ * coefficients by writing the tensor.  cfg's four are still checked as sg_ppo_grad_device checks them; the tensor's VALUES ARE NOT
+ * CHECKED (as sg_dqn_act_device's epsilon_dev): clip_range_vf <= 0 or NaN turns value clipping off for that member, by the comparison,
+ * and a value the host would have refused -- a NaN or negative ent_coef, say -- affects that member's outputs only.  With member_coef
+ * and a critic, batch.old_value is required: any member may turn value clipping on.  normalize_advantage and adv_epsilon are per call.
+ * Launches: the advantage statistics (when normalising) with Gadv = min(ceil(n / 1024), max(1, 256 / members)) workgroups per member,
+ * the backward with sg_policy_population_grad_device's G = min(ceil(n / R), max(1, 256 / members)) per member, and the reduction with
+ * one statistics workgroup per member.  Allocates nothing, never synchronises, hipGraph-capturable; no atomics: the same inputs and the
+ * same n give the same bits.
+ * BIT-EQUALITY RULE.  Member m's gradient slices, its twelve statistics and its per-row outputs are bit for bit sg_ppo_grad_device's
+ * on an sg_policy over member m's parameter slices with index[m] and member m's coefficients whenever the member's entries group as the
+ * single call groups them, that is when both
+ *     ceil(n / R) <= 256 / members      (the parameter partials and the statistics sums; R = 256, 128 or 64 by the hidden width)
+ *     ceil(n / 1024) <= 256 / members   (the advantage partials)
+ * hold (integer division).  Beyond either it is the same sums in another grouping: close, not bit-equal.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): whatever the population calls refuse of policy and members; whatever
+ * sg_ppo_grad_device refuses; members x n above 2^31 - 1; members x n > rows without an index; a workspace smaller than
+ * sg_ppo_population_grad_workspace_bytes(env, policy, members, n) or not aligned to 8 bytes; member_coef with a critic and no old_value. */
+int sg_ppo_population_grad_device(sg_env *env, const sg_policy *policy, int32_t members, const sg_ppo_config *cfg, const sg_ppo_batch *batch,
+                                  const float *member_coef, int64_t rows, int64_t n, const sg_policy_grads *grads, float *stats_out,
+                                  const sg_ppo_rows *row_out, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_ppo_population_grad_device needs for n entries per member: the parameter partials [members][G][parameters]
+ * rounded up to 8 bytes, double [members][Gadv][2], float [members][G][8]; 0 and an error message for an invalid policy, members or n */
+size_t sg_ppo_population_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int32_t members, int64_t n);
+
 /* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
  * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
  * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.

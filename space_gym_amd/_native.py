@@ -286,6 +286,9 @@ SYMBOLS = {
     "sg_policy_population_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp,
                                                    C.POINTER(SgPolicyGrads), _vp, C.c_size_t, _vp]),
     "sg_policy_population_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64]),
+    "sg_ppo_population_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, C.POINTER(SgPpoConfig), C.POINTER(SgPpoBatch), _vp, C.c_int64,
+                                                C.c_int64, C.POINTER(SgPolicyGrads), _vp, C.POINTER(SgPpoRows), _vp, C.c_size_t, _vp]),
+    "sg_ppo_population_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -299,7 +299,7 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "squashed_sample_torch", "squashed_sample_raw_torch", "squashed_grad_torch", "dqn_torch", "dqn_act_torch", "rollout_dqn_torch",
                "dqn_evaluate_torch", "dqn_evaluate_raw_torch", "dqn_grad_torch", "policy_population_torch", "population_member_torch",
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
-               "population_grad_torch")
+               "population_grad_torch", "population_ppo_grad_torch")
 
 
 class SpaceGymVectorEnv:
@@ -1555,9 +1555,35 @@ class SpaceGymVectorEnv:
         ppo_stats_names (stats: the tensor to fill).  rows: optional dict logp / value / g_logp / g_value of float32 [n] tensors that
         receive the per-row numbers the kernel used.  ppo_assign_grads hands the gradients to an optimizer.  Same inputs and same n:
         the same bits."""
-        import math
         import torch
         self._net_handle(policy, Policy)
+        obs, R, need = self._ppo_batch(policy, batch, clip_range, clip_range_vf, ent_coef, vf_coef)
+        if index is None:
+            n = R
+        else:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1 or int(index.shape[0]) < 1:
+                raise ValueError("index: expected an int64 CUDA tensor of shape (n,) with n >= 1")
+            n = int(index.shape[0])
+            self._check_tensor("index", index, torch.int64, (n,))
+        if normalize_advantage and n < 2:
+            raise ValueError("normalize_advantage: needs n >= 2")
+        out, g = self._policy_grads(policy, out, "policy", policy.has_critic, "the policy has a critic; its gradients need tensors")
+        if stats is None:
+            stats = obs.new_empty(len(self.ppo_stats_names))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (len(self.ppo_stats_names),))
+        r = self._ppo_rows(policy, rows, (n,), "policy")
+        cfg, b = self._ppo_structs(policy, batch, need, index, clip_range, clip_range_vf, ent_coef, vf_coef, normalize_advantage)
+        ws = self._grad_workspace(policy, "sg_ppo_grad_workspace_bytes", n, obs.device, "ppo_grad_torch", "sg_ppo_grad_workspace_bytes")
+        self._ck(self._lib.sg_ppo_grad_device(self._h, C.byref(policy.struct), C.byref(cfg), C.byref(b), R, n, C.byref(g), _ptr(stats),
+                                              C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()), "sg_ppo_grad_device")
+        return out, stats
+
+    def _ppo_batch(self, handle, batch, clip_range, clip_range_vf, ent_coef, vf_coef, coef=False):
+        """checks the batch dict and the four host coefficients of ppo_grad_torch / population_ppo_grad_torch; coef: a coefficient
+        tensor is given, which makes batch['value'] necessary beside a critic.  Returns (obs, rows, the columns needed beside obs and action)"""
+        import math
+        import torch
         if not isinstance(batch, dict):
             raise ValueError("batch: expected a dict obs / action / logp / advantage / ret / value of flattened CUDA tensors")
         obs = batch.get("obs")
@@ -1573,25 +1599,18 @@ class SpaceGymVectorEnv:
         for name, v in (("ent_coef", ent_coef), ("vf_coef", vf_coef)):
             if not v >= 0 or math.isinf(v):
                 raise ValueError(f"{name}: expected a finite value >= 0, got {v}")
-        need = ["logp", "advantage"] + (["ret"] if policy.has_critic else []) + (["value"] if policy.has_critic and clip_range_vf is not None else [])
+        value = handle.has_critic and (clip_range_vf is not None or coef)
+        need = ["logp", "advantage"] + (["ret"] if handle.has_critic else []) + (["value"] if value else [])
         for k in need:
             if batch.get(k) is None:
-                raise ValueError(f"batch['{k}']: missing" + (" (clip_range_vf is given)" if k == "value" else ""))
+                why = " (clip_range_vf is given)" if clip_range_vf is not None else " (coef is given: any member may turn value clipping on)"
+                raise ValueError(f"batch['{k}']: missing" + (why if k == "value" else ""))
             self._check_tensor(f"batch['{k}']", batch[k], torch.float32, (R,))
-        if index is None:
-            n = R
-        else:
-            if not isinstance(index, torch.Tensor) or index.dim() != 1 or int(index.shape[0]) < 1:
-                raise ValueError("index: expected an int64 CUDA tensor of shape (n,) with n >= 1")
-            n = int(index.shape[0])
-            self._check_tensor("index", index, torch.int64, (n,))
-        if normalize_advantage and n < 2:
-            raise ValueError("normalize_advantage: needs n >= 2")
-        out, g = self._policy_grads(policy, out, "policy", policy.has_critic, "the policy has a critic; its gradients need tensors")
-        if stats is None:
-            stats = obs.new_empty(len(self.ppo_stats_names))
-        else:
-            self._check_tensor("stats", stats, torch.float32, (len(self.ppo_stats_names),))
+        return obs, R, need
+
+    def _ppo_rows(self, handle, rows, shape, noun):
+        """the sg_ppo_rows of the optional per-row outputs, each float32 of `shape`"""
+        import torch
         r = _native.SgPpoRows()
         if rows is not None:
             for k, t in rows.items():
@@ -1599,22 +1618,23 @@ class SpaceGymVectorEnv:
                     raise ValueError(f"rows['{k}']: expected the keys logp, value, g_logp, g_value")
                 if t is None:
                     continue
-                if k in ("value", "g_value") and not policy.has_critic:
-                    raise ValueError(f"rows['{k}']: the policy has no critic")
-                self._check_tensor(f"rows['{k}']", t, torch.float32, (n,))
+                if k in ("value", "g_value") and not handle.has_critic:
+                    raise ValueError(f"rows['{k}']: the {noun} has no critic")
+                self._check_tensor(f"rows['{k}']", t, torch.float32, shape)
                 setattr(r, k, t.data_ptr())
+        return r
+
+    def _ppo_structs(self, handle, batch, need, index, clip_range, clip_range_vf, ent_coef, vf_coef, normalize_advantage):
+        """(sg_ppo_config, sg_ppo_batch) of a checked call"""
         cfg = _native.SgPpoConfig()
         self._lib.sg_ppo_config_init(C.byref(cfg))
         cfg.clip_range, cfg.clip_range_vf = clip_range, clip_range_vf if clip_range_vf is not None else 0.0
         cfg.ent_coef, cfg.vf_coef, cfg.normalize_advantage = ent_coef, vf_coef, int(bool(normalize_advantage))
-        b = _native.SgPpoBatch(obs=obs.data_ptr(), action=batch["action"].data_ptr(), old_logp=batch["logp"].data_ptr(),
-                               advantage=batch["advantage"].data_ptr(), ret=batch["ret"].data_ptr() if policy.has_critic else None,
+        b = _native.SgPpoBatch(obs=batch["obs"].data_ptr(), action=batch["action"].data_ptr(), old_logp=batch["logp"].data_ptr(),
+                               advantage=batch["advantage"].data_ptr(), ret=batch["ret"].data_ptr() if handle.has_critic else None,
                                old_value=batch["value"].data_ptr() if "value" in need else None,
                                index=index.data_ptr() if index is not None else None)
-        ws = self._grad_workspace(policy, "sg_ppo_grad_workspace_bytes", n, obs.device, "ppo_grad_torch", "sg_ppo_grad_workspace_bytes")
-        self._ck(self._lib.sg_ppo_grad_device(self._h, C.byref(policy.struct), C.byref(cfg), C.byref(b), R, n, C.byref(g), _ptr(stats),
-                                              C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()), "sg_ppo_grad_device")
-        return out, stats
+        return cfg, b
 
     @staticmethod
     def ppo_assign_grads(policy, grads):
@@ -1742,6 +1762,54 @@ class SpaceGymVectorEnv:
                                                             _ptr(g_value), C.byref(g), _ptr(ws), ws.numel(), self._stream()),
                  "sg_policy_population_grad_device")
         return out
+
+    ppo_coef_names = ("clip_range", "clip_range_vf", "ent_coef", "vf_coef")  # the columns of population_ppo_grad_torch's coef [P, 4]
+
+    def population_ppo_grad_torch(self, pop, batch, index=None, coef=None, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5,
+                                  normalize_advantage=True, out=None, stats=None, rows=None):
+        """ppo_grad_torch for every member of a population in one call (sg_ppo_population_grad_device: two or three launches, no host
+        synchronisation, graph-capturable after one warm-up call with the same n).  batch: ppo_grad_torch's dict, ONE flattened
+        rollout of `rows` rows shared by all members (the [K, B] buffers of rollout_population_torch and gae_torch, reshaped).  index:
+        int64 [P, n], entry (m, i) the row member m's minibatch entry i reads -- the gather puts a member's env block into its
+        minibatch; repeats allowed, an entry outside [0, rows) handled as ppo_grad_torch's; None: member m takes rows [m n, (m + 1) n),
+        n = rows // P.  coef: optional float32 CUDA tensor [P, 4] of per-member (clip_range, clip_range_vf, ent_coef, vf_coef), the
+        columns named by ppo_coef_names; given, it replaces the four scalars for every member and is READ ON THE DEVICE at every
+        call or graph replay; its values are not checked (clip_range_vf <= 0 or NaN: no value clipping for that member; a value the
+        scalars would be refused for affects that member's outputs only), and with a critic batch['value'] is needed.  The scalars
+        are checked as ppo_grad_torch checks them.  Returns (grads, stats): grads the dict of STACKED tensors population_grad_torch
+        returns, written; stats float32 [P, 12] named by ppo_stats_names.  rows: optional dict logp / value / g_logp / g_value of
+        float32 [P, n].  Member m's slices, statistics and rows are bit for bit ppo_grad_torch's on population_member_torch(pop, m)
+        with index[m] and member m's coefficients while ceil(n / R) <= 256 // P (R = 256, 128 or 64 by the hidden width) and
+        ceil(n / 1024) <= 256 // P; beyond that the same sums in another grouping.  Same inputs and same n: the same bits."""
+        import torch
+        P = self._population(pop)
+        if coef is not None:
+            self._check_tensor("coef", coef, torch.float32, (P, len(self.ppo_coef_names)))
+        obs, R, need = self._ppo_batch(pop, batch, clip_range, clip_range_vf, ent_coef, vf_coef, coef=coef is not None)
+        if index is None:
+            n = R // P
+            if n < 1:
+                raise ValueError(f"index: None gives member m the rows [m n, (m + 1) n), but the batch holds {R} rows for {P} members")
+        else:
+            if not isinstance(index, torch.Tensor) or index.dim() != 2 or int(index.shape[0]) != P or int(index.shape[1]) < 1:
+                raise ValueError(f"index: expected an int64 CUDA tensor of shape ({P}, n) with n >= 1")
+            n = int(index.shape[1])
+            self._check_tensor("index", index, torch.int64, (P, n))
+        if normalize_advantage and n < 2:
+            raise ValueError("normalize_advantage: needs n >= 2")
+        out, g = self._policy_grads(pop, out, "population", pop.has_critic, "the population has a critic; its gradients need tensors")
+        if stats is None:
+            stats = obs.new_empty((P, len(self.ppo_stats_names)))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (P, len(self.ppo_stats_names)))
+        r = self._ppo_rows(pop, rows, (P, n), "population")
+        cfg, b = self._ppo_structs(pop, batch, need, index, clip_range, clip_range_vf, ent_coef, vf_coef, normalize_advantage)
+        ws = self._grad_workspace(pop, "sg_ppo_population_grad_workspace_bytes", n, obs.device, "population_ppo_grad_torch",
+                                  "sg_ppo_population_grad_workspace_bytes", members=P)
+        self._ck(self._lib.sg_ppo_population_grad_device(self._h, C.byref(pop.struct), P, C.byref(cfg), C.byref(b), _ptr(coef), R, n, C.byref(g),
+                                                         _ptr(stats), C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(),
+                                                         self._stream()), "sg_ppo_population_grad_device")
+        return out, stats
 
     def population_evaluate_torch(self, pop, obs, action):
         """logp, entropy, value, each [P, n], of the stored rows under the CURRENT parameters, differentiable with respect to the

@@ -1030,62 +1030,67 @@ class SpaceGymVectorEnv:
             self._episode_stats = True
             self._blocks = {}
 
-    def _snapshot_has_episodes(self, blob):
-        v = self._snapshot_version(blob)
-        return v == 2 or (v == 3 and bool(self._snapshot_flags(blob) & 1))
+    SNAPSHOT_HEADER_BYTES = 48  # sizeof(SnapshotHeader), which csrc/sg_engine.hip pins with a static_assert
 
-    def _snapshot_flags(self, blob):
-        """the flags word of a version-3 blob (1: episode block, 2: normalization block), right after the columns"""
-        return int(np.frombuffer(blob, dtype=np.uint32, count=1, offset=self.SNAPSHOT_HEADER_BYTES + self._column_bytes())[0])
+    def _snapshot_blocks(self, version, flags=0, n_profiles=0):
+        """(name, dtype, shape) of the blocks of a blob of this env, in order: the mirror of snapshot_layout() in
+        csrc/sg_engine.hip, where the format is described (norm_mean, norm_var, norm_count are its norm_stats block).  Like
+        there, a reader that does not know flags or n_profiles yet passes 0: the blocks before the word that holds them stay"""
+        B, S, goal = self.num_envs, self.obs_dim + 1, self.spec["family"] == "goal"
+        eps, nrm, prf = flags & 1, flags & 2, flags & 4
+        table = [("header", np.uint8, (self.SNAPSHOT_HEADER_BYTES,), True),
+                 ("q0", np.float32, (B, 4), True), ("q1", np.float32, (B, 4), True),
+                 ("ctr", np.uint32, (B, 2), True), ("aux", np.uint32, (B, 4), True),
+                 ("pl0", np.float32, (B, 4), goal), ("pl1", np.float32, (B, 4), goal and self.n_planets > 2),
+                 ("cshift", np.float32, (B, 4), goal), ("orbd", np.float64, (B, 2), self.env_id == "KeplerRandomOrbits-v0"),
+                 ("flags", np.uint32, (1, 2), version == 3),
+                 ("ep_ret", np.float64, (B, 1), eps), ("ep_len", np.int32, (B, 1), eps),
+                 ("norm_config", np.uint8, (C.sizeof(_native.SgNormalize),), nrm),
+                 ("norm_mean", np.float64, (S,), nrm), ("norm_var", np.float64, (S,), nrm), ("norm_count", np.float64, (S,), nrm),
+                 ("norm_returns", np.float64, (B,), nrm),
+                 ("profile_count", np.uint32, (2,), prf),
+                 ("profiles", np.uint8, (n_profiles * C.sizeof(_native.SgRewardProfile),), prf),
+                 ("profile_index", np.uint8, (B,), prf)]
+        return [row[:3] for row in table if row[3]]
 
-    def _snapshot_column_specs(self):
-        cols = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4)]
-        if self.spec["family"] == "goal":
-            cols += [("pl0", np.float32, 4)] + ([("pl1", np.float32, 4)] if self.n_planets > 2 else []) + [("cshift", np.float32, 4)]
-        elif self.env_id == "KeplerRandomOrbits-v0":
-            cols += [("orbd", np.float64, 2)]
-        return cols
-
-    def _column_bytes(self):
-        return sum(self.num_envs * w * np.dtype(dt).itemsize for _, dt, w in self._snapshot_column_specs())
+    def _snapshot_views(self, blob, blocks):
+        """{name: view of the blob} of `blocks`, and where the last one ends"""
+        off, out = 0, {}
+        for name, dt, shape in blocks:
+            n = int(np.prod(shape))
+            out[name] = np.frombuffer(blob, dtype=dt, count=n, offset=off).reshape(shape)
+            off += out[name].nbytes
+        return out, off
 
     @staticmethod
     def _snapshot_version(blob):
         return int(np.frombuffer(blob, dtype=np.uint32, count=2)[1])
 
-    SNAPSHOT_HEADER_BYTES = 48
+    def _snapshot_flags(self, blob):
+        """which blocks follow the columns (1: episode statistics, 2: normalization, 4: reward profiles): the flags word of a
+        version-3 blob; versions 1 and 2 are flags 0 and 1 without the word"""
+        version = self._snapshot_version(blob)
+        if version < 3:
+            return int(version == 2)
+        return int(self._snapshot_views(blob, self._snapshot_blocks(3))[0]["flags"][0, 0])
+
+    def _snapshot_has_episodes(self, blob):
+        return bool(self._snapshot_flags(blob) & 1)
 
     def snapshot_columns(self, blob):
-        """introspection of a save_state() blob: the engine's per-env columns as NumPy views --
-        q0 (x, y, theta, vx), q1 (vy, omega, goal_x, goal_y | orbit angle, eccentricity), ctr (elapsed, episode),
-        aux (goal draws, ship_tile | goal_tile << 8 | case_b << 16 | flip << 17, free-tile multiset lo, hi),
+        """introspection of a save_state() blob: its blocks (all but the header) as NumPy views under the names of
+        _snapshot_blocks -- q0 (x, y, theta, vx), q1 (vy, omega, goal_x, goal_y | orbit angle, eccentricity), ctr (elapsed,
+        episode), aux (goal draws, ship_tile | goal_tile << 8 | case_b << 16 | flip << 17, free-tile multiset lo, hi),
         Goal: pl0 / pl1 (two planets each), cshift (tiling column shifts); KeplerRandomOrbits: orbd (cos, sin of the angle);
-        a blob taken with episode statistics on: ep_ret (float64), ep_len (int32), the running return and length;
-        one taken with normalization on (version 3): flags, norm_config (sg_normalize bytes), norm_mean / norm_var /
-        norm_count (float64 [D + 1], the last entry the return's) and norm_returns (float64 [B])"""
-        B, off, out = self.num_envs, self.SNAPSHOT_HEADER_BYTES, {}
-        cols = self._snapshot_column_specs()
-        version = self._snapshot_version(blob)
-        flags = self._snapshot_flags(blob) if version == 3 else (1 if version == 2 else 0)
-        if version == 3:
-            cols += [("flags", np.uint32, 2)]
-        if flags & 1:
-            cols += [("ep_ret", np.float64, 1), ("ep_len", np.int32, 1)]
-        for name, dt, w in cols:
-            n = (1 if name == "flags" else B) * w
-            out[name] = np.frombuffer(blob, dtype=dt, count=n, offset=off).reshape(-1, w)
-            off += n * np.dtype(dt).itemsize
-        if flags & 2:
-            nb = C.sizeof(_native.SgNormalize)
-            out["norm_config"] = blob[off:off + nb]
-            off += nb
-            S = self.obs_dim + 1
-            for name in ("norm_mean", "norm_var", "norm_count"):
-                out[name] = np.frombuffer(blob, dtype=np.float64, count=S, offset=off)
-                off += 8 * S
-            out["norm_returns"] = np.frombuffer(blob, dtype=np.float64, count=B, offset=off)
-            off += 8 * B
+        then what the blob was taken with: flags, ep_ret / ep_len, norm_config (sg_normalize bytes) and norm_*,
+        profile_count (n, 0), profiles (sg_reward_profile bytes) and profile_index.  Raises if they do not add up to the blob"""
+        version, flags = self._snapshot_version(blob), self._snapshot_flags(blob)
+        n_profiles = 0
+        if flags & 4:
+            n_profiles = int(self._snapshot_views(blob, self._snapshot_blocks(version, flags))[0]["profile_count"][0])
+        out, off = self._snapshot_views(blob, self._snapshot_blocks(version, flags, n_profiles))
         assert off == blob.size, (off, blob.size)
+        del out["header"]
         return out
 
     # ------------------------------------------------------------------ device-resident snapshots

@@ -162,6 +162,53 @@ def test_snapshot_columns_reads_a_version_3_blob():
         assert env._snapshot_has_episodes(blob) == bool(flags & 1)
 
 
+@pytest.mark.parametrize("version,flags", [(1, 0), (2, 1)] + [(3, f) for f in range(8)])
+@pytest.mark.parametrize("stub", ["goal4p", "kepler_random"])
+def test_snapshot_columns_reads_every_version_and_combination_of_blocks(stub, version, flags):
+    """blobs put together by hand, block after block, for every flags word and for versions 1 and 2 (flags 0 and 1 without the
+    word); 5 envs, so the int32 lengths leave every later float64 block at an offset that is no multiple of 8"""
+    from space_gym_amd import _native
+    from space_gym_amd.vector_env import SpaceGymVectorEnv
+    B, D, P = 5, {"goal4p": 14, "kepler_random": 7}[stub], 3
+    env = _stub_env(B=B, D=D)
+    if stub == "goal4p":
+        env.spec, env.env_id, env.n_planets = {"family": "goal"}, "GoalContinuous4P-v0", 4
+        columns = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4),
+                   ("pl0", np.float32, 4), ("pl1", np.float32, 4), ("cshift", np.float32, 4)]
+    else:
+        env.spec, env.env_id, env.n_planets = {"family": "kepler"}, "KeplerRandomOrbits-v0", 0
+        columns = [("q0", np.float32, 4), ("q1", np.float32, 4), ("ctr", np.uint32, 2), ("aux", np.uint32, 4), ("orbd", np.float64, 2)]
+    rng = np.random.default_rng(version * 8 + flags)
+
+    def block(dtype, shape):
+        raw = rng.integers(0, 256, int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=np.uint8)
+        return raw.view(dtype).reshape(shape)
+
+    expect = {name: block(dt, (B, w)) for name, dt, w in columns}
+    if version == 3:
+        expect["flags"] = np.array([[flags, 0]], np.uint32)
+    if flags & 1:
+        expect.update(ep_ret=block(np.float64, (B, 1)), ep_len=block(np.int32, (B, 1)))
+    if flags & 2:
+        expect.update(norm_config=block(np.uint8, (C.sizeof(_native.SgNormalize),)), norm_mean=block(np.float64, (D + 1,)),
+                      norm_var=block(np.float64, (D + 1,)), norm_count=block(np.float64, (D + 1,)), norm_returns=block(np.float64, (B,)))
+    if flags & 4:
+        expect.update(profile_count=np.array([P, 0], np.uint32), profiles=block(np.uint8, (P * C.sizeof(_native.SgRewardProfile),)),
+                      profile_index=block(np.uint8, (B,)))
+    hdr = np.zeros(SpaceGymVectorEnv.SNAPSHOT_HEADER_BYTES, np.uint8)
+    hdr[4:8] = np.frombuffer(np.uint32(version).tobytes(), np.uint8)
+    blob = np.frombuffer(hdr.tobytes() + b"".join(v.tobytes() for v in expect.values()), np.uint8)
+    out = env.snapshot_columns(blob)
+    assert list(out) == list(expect)
+    for name, want in expect.items():
+        assert out[name].dtype == want.dtype and out[name].shape == want.shape, name
+        assert out[name].tobytes() == want.tobytes(), name
+    assert env._snapshot_version(blob) == version and env._snapshot_flags(blob) == flags
+    assert env._snapshot_has_episodes(blob) == bool(flags & 1)
+    with pytest.raises(AssertionError):  # the blocks must add up to the blob
+        env.snapshot_columns(np.concatenate([blob, np.zeros(1, np.uint8)]))
+
+
 def _pooled(batches, ddof_prior=True):
     """RunningMeanStd after updates with `batches` is the pooled mean / variance of the prior (count 1e-4 at mean 0, var 1)
     and every value seen -- exactly, in rational arithmetic"""

@@ -1,5 +1,6 @@
 """Builds libspacegym_hip.so (HIP kernels for gfx950 + the C ABI of include/spacegym.h) in-tree with hipcc."""
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -29,10 +30,10 @@ def flags(extra=()):
             "-I", os.path.join(ROOT, "include"), "-I", CSRC, *extra]
 
 
-def is_stale():
-    if not os.path.exists(LIB):
+def is_stale(target=LIB):
+    if not os.path.exists(target):
         return True
-    t = os.path.getmtime(LIB)
+    t = os.path.getmtime(target)
     deps = [os.path.join(CSRC, f) for f in SOURCES] + [f if os.path.isabs(f) else os.path.join(CSRC, f) for f in HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -48,6 +49,45 @@ def build(force=False, verbose=False, extra=(), out=None):
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return out
+
+
+def device_asm(force=False):
+    """One device-only compile for the tests and tools that inspect the code: (assembly, the compiler's resource remarks), kept
+    until a source is newer.  Both are written under temporary names and renamed at the end: a file that is there is whole."""
+    out = [os.path.join(LIB_DIR, "sg_engine.s"), os.path.join(LIB_DIR, "sg_engine.remarks.txt")]
+    if not force and not any(is_stale(f) for f in out):
+        return tuple(out)
+    os.makedirs(LIB_DIR, exist_ok=True)
+    tmp = ["%s.%d.tmp" % (f, os.getpid()) for f in out]
+    cmd = [hipcc(), *[f for f in flags() if f not in ("-shared", "-fPIC")], "-S", "--cuda-device-only",
+           "-Rpass-analysis=kernel-resource-usage", "-o", tmp[0], *[os.path.join(CSRC, f) for f in SOURCES]]
+    try:
+        with open(tmp[1], "w") as err:
+            failed = subprocess.call(cmd, stderr=err)
+        if failed:
+            raise RuntimeError("device-only compile failed:\n" + open(tmp[1]).read()[-4000:])
+        for t, f in zip(tmp, out):
+            os.replace(t, f)
+    finally:
+        for t in filter(os.path.exists, tmp):
+            os.remove(t)
+    return tuple(out)
+
+
+def resource_report(remarks_path=None):
+    """One dict per kernel of the compiler's resource remarks: `name` (mangled) and the remark keys ("VGPRs", ...) as strings."""
+    rows, cur = [], None
+    for line in open(remarks_path or device_asm()[1]):
+        m = re.search(r"remark: \s*(.+?)\s*\[-Rpass-analysis", line)
+        if not m:
+            continue
+        k, _, v = m.group(1).partition(":")
+        if k.strip() == "Function Name":
+            cur = {"name": v.strip()}
+            rows.append(cur)
+        elif cur is not None:
+            cur[k.strip()] = v.strip()
+    return rows
 
 
 if __name__ == "__main__":

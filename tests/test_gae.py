@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import engine_asm
 from gae_model import dense_from_list, gae_model, gae_model_f64, synthetic
 from test_episode_stats import _fake_cuda, _stub_env
-from test_snapshot_device import _function_body, _header_args
+from test_snapshot_device import _header_args
 
 DEVICE_ARGS = ["sg_env *env", "int32_t n_steps", "const sg_gae_config *cfg", "const float *reward_dev", "const uint8_t *done_dev",
                "const uint8_t *truncated_dev", "const float *value_dev", "const float *last_value_dev",
@@ -298,9 +299,9 @@ def test_the_status_message_of_a_refused_value_list_is_reachable():
     code = int(re.search(r"constexpr int kStatusGaeList = (\d+);", inc).group(1))
     others = [int(v) for v in re.findall(r"constexpr int kStatus\w+ = (\d+);", src)]
     assert code not in others and code > 3  # (1 .. 3: the rollout kernels' hand-off waits)
-    assert len(re.findall(r"\*status = kStatusGaeList;", _function_body(inc, "void gae_scatter_kernel("))) == 2  # count, record
+    assert len(re.findall(r"\*status = kStatusGaeList;", engine_asm.function_body(inc, "void gae_scatter_kernel("))) == 2  # count, record
     for sig in ("static int status_error(sg_env *e, const char *who)", 'extern "C" int sg_check_status(sg_env *e)'):
-        assert re.search(r"if \(st == kStatusGaeList\)\s*return fail\(", _function_body(src, sig)), sig
+        assert re.search(r"if \(st == kStatusGaeList\)\s*return fail\(", engine_asm.function_body(src, sig)), sig
     lib = open(build.build(), "rb").read()
     assert b"sg_gae_device: a value list with count > capacity" in lib
     assert b"an earlier sg_gae_device was given a value list" in lib
@@ -311,33 +312,21 @@ def test_the_new_kernels_build_for_gfx950_without_scratch():
     kernel use no scratch, spill no vector register and need no LDS; the scan kernels fit 4 waves per SIMD (<= 128 VGPRs), so a
     batch of 1 048 576 envs hides latency by occupancy as well; every instruction of theirs that writes memory is a
     global_store_* of one element (dword), and none is wider: nothing assumes more than 4-byte alignment"""
-    import shutil
-    import subprocess
-    import tempfile
     from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
+    engine_asm.text()  # (skips without a compiler)
     lib = open(build.build(), "rb").read()
     for name in (b"sg_gae_config_init", b"sg_gae_device", b"sg_gae", b"gae_scan_kernel", b"gae_scatter_kernel"):
         assert name in lib
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        text = open(asm).read()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*(?:gae_scan_kernel|gae_scatter_kernel)\S*)\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    kernels = engine_asm.descriptors(r"\S*(?:gae_scan_kernel|gae_scatter_kernel)\S*")
     assert len(kernels) == 5, [k for k, _ in kernels]  # gae_scan_kernel<value?, terminal?> x 4, gae_scatter_kernel
-    for name, body in kernels:
-        field = lambda k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))  # noqa: E731
-        assert field("private_segment_fixed_size") == 0, name
-        assert field("group_segment_fixed_size") == 0, name
-        assert field("next_free_vgpr") <= 128, name
-    spills = re.findall(r"\.name:\s+(\S*(?:gae_scan_kernel|gae_scatter_kernel)\S*)(?:(?!\.name:).)*?\.vgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(spills) == 5 and all(int(n) == 0 for _, n in spills), spills
+    for name, field in kernels:
+        assert field["private_segment_fixed_size"] == 0, name
+        assert field["group_segment_fixed_size"] == 0, name
+        assert field["next_free_vgpr"] <= 128, name
+    spills = engine_asm.spill_counts(r"\S*(?:gae_scan_kernel|gae_scatter_kernel)\S*")
+    assert len(spills) == 5 and all(n == 0 for _, n in spills), spills
     for name, _ in kernels:
-        st = text.index("\n" + name + ":")
-        fn = text[st:text.index(".Lfunc_end", st)]
+        fn = engine_asm.function(name)
         writes = re.findall(r"^\s+(\w*(?:store|atomic)\w*)\s", fn, flags=re.M)
         assert writes and all(w == "global_store_dword" for w in writes), (name, sorted(set(writes)))
         loads = set(re.findall(r"^\s+(global_load_\w+)\s", fn, flags=re.M))

@@ -123,23 +123,8 @@ def test_no_vector_register_spills_in_the_default_kernels():
     registers more and the compiler spills to scratch inside the step loops (measured: +40 % per step).  The compiler's
     own resource report (hipcc -Rpass-analysis=kernel-resource-usage, no GPU needed) must show no vector spill for any
     kernel of the library."""
-    import re, shutil, subprocess
-    from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    cmd = [build.hipcc(), *build.flags(("-Rpass-analysis=kernel-resource-usage",)), "-o", os.devnull, os.path.join(build.CSRC, "sg_engine.hip")]
-    err = subprocess.run(cmd, capture_output=True, text=True, timeout=900).stderr
-    rows, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: \s*(.+?)\s*\[-Rpass-analysis", line)
-        if not m:
-            continue
-        k, _, v = m.group(1).partition(":")
-        if k.strip() == "Function Name":
-            cur = {"name": v.strip()}
-            rows.append(cur)
-        elif cur is not None:
-            cur[k.strip()] = v.strip()
+    import engine_asm
+    rows = engine_asm.resource_rows()
     assert len(rows) >= 40  # every kernel of the library reported
     spilled = {r["name"]: int(r["VGPRs Spill"]) for r in rows if int(r.get("VGPRs Spill", "0")) > 0}
     assert not spilled, spilled
@@ -153,30 +138,9 @@ def test_step_kernels_wait_for_memory_only_at_the_top_of_a_pass():
     memory (with the inputs loaded into registers the compiler had put a wait for everything behind the stores and waits and
     copies right behind the loads: 59.9 instead of 53.8 us per launch at 1 048 576 envs).  Checked on the device assembly (no GPU
     needed): behind the loop's group of LDS-DMA loads at least 300 instructions follow without an `s_waitcnt vmcnt`."""
-    import re, shutil, subprocess, tempfile
-    from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        lines = open(asm).read().splitlines()
-    starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\d+(goal|kepler)_step_kernelI\w*:", l)]
-    assert len(starts) == 8  # 2P / 3P / 4P x two steerings, Kepler x two steerings
-    for st in starts:
-        end = next(i for i in range(st, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        ins = [l.split(";")[0].strip() for l in lines[st + 1:end]]
-        ins = [l for l in ins if l and not l.startswith(".") and not l.endswith(":")]
-        dma = [k for k, l in enumerate(ins) if l.startswith("global_load_lds")]
-        assert len(dma) >= 14, lines[st]  # the prologue's group and the loop's
-        last = dma[-1]
-        nxt = next((k for k in range(last + 1, len(ins)) if ins[k].startswith("s_waitcnt") and "vmcnt" in ins[k]), len(ins))
-        assert nxt - last >= 300, (lines[st], nxt - last)
-        # and nothing but address arithmetic between the loads of the group
-        first = next(k for k in dma if last - k < 120)
-        assert not any(l.startswith("s_waitcnt") and "vmcnt" in l for l in ins[first:last]), lines[st]
+    import engine_asm
+    # 2P / 3P / 4P x two steerings, Kepler x two steerings; the prologue's group and the loop's, only address arithmetic within it
+    engine_asm.assert_no_memory_wait_behind_dma(r"^_Z\d+(goal|kepler)_step_kernelI\w*:", n_kernels=8, min_dma=14)
 
 
 def test_fast_step_coefficients_satisfy_the_order_conditions():

@@ -9,12 +9,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import engine_asm
 from priority_model import STREAM_PRIORITY, Priorities, quantise, umul64hi_64
 from replay_model import philox4x32_10
 from test_episode_stats import _fake_cuda
 from test_gae import _struct_fields
 from test_replay import B, D, T, _env, _ring, _ring_arg_matches, _tlist
-from test_snapshot_device import _function_body, _header_args
+from test_snapshot_device import _header_args
 
 
 # ---------------------------------------------------------------------------------------------- declarations
@@ -358,9 +359,9 @@ def test_the_status_message_of_a_refused_priority_call_is_reachable():
     others = "".join(open(os.path.join(build.CSRC, f)).read() for f in ("sg_engine.hip", "sg_gae.inc", "sg_replay.inc", "sg_device.hpp"))
     assert 9 not in [int(v) for v in re.findall(r"constexpr int kStatus\w+ = (\d+);", others)]
     assert re.search(r"constexpr uint32_t kStreamPriority = 4u;", inc)
-    assert "kStreamPriority, w)" in _function_body(inc, "void priority_draw_kernel(")
+    assert "kStreamPriority, w)" in engine_asm.function_body(inc, "void priority_draw_kernel(")
     for sig in ("static int status_error(sg_env *e, const char *who)", 'extern "C" int sg_check_status(sg_env *e)'):
-        assert re.search(r"if \(st == kStatusPriority\)\s*return fail\(", _function_body(src, sig)), sig
+        assert re.search(r"if \(st == kStatusPriority\)\s*return fail\(", engine_asm.function_body(src, sig)), sig
     lib = open(build.build(), "rb").read()
     assert b"sg_priority_*_device: priorities without a matching header" in lib
     assert b"an earlier sg_priority_*_device call refused its input on the device" in lib
@@ -370,39 +371,27 @@ def test_the_new_kernels_build_for_gfx950_without_scratch():
     """In the code object the priority kernels use no scratch and spill no register; only the one-workgroup top kernel needs LDS
     (one level of at most 64 sums: 512 B); the draw kernel stays within 128 VGPRs; no instruction writes memory through the scalar
     unit, scratch, flat or buffer addressing; the integer atomics are the update's and they are global_atomic_* instructions"""
-    import shutil
-    import subprocess
-    import tempfile
     from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
+    engine_asm.text()  # (skips without a compiler)
     lib = open(build.build(), "rb").read()
     for name in (b"sg_priority_bytes", b"sg_priority_begin_device", b"sg_priority_commit_device", b"sg_priority_update_device",
                  b"sg_priority_sample_device", b"sg_priority_sample_config_init", b"priority_draw_kernel", b"priority_commit_kernel",
                  b"priority_update_kernel", b"priority_level_kernel", b"priority_top_kernel", b"priority_begin_kernel"):
         assert name in lib
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        text = open(asm).read()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*priority_\w+_kernel\S*)\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    kernels = engine_asm.descriptors(r"\S*priority_\w+_kernel\S*")
     # begin, commit, update<0 | 1>, level, top, tick, draw
     assert len(kernels) == 8, [k for k, _ in kernels]
-    for name, body in kernels:
+    for name, field in kernels:
         assert not re.search(r"replay_\w+_kernel|profile|snapshot_kernel|_restore_kernel|gae_\w+_kernel", name), name
-        field = lambda k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))  # noqa: E731
-        assert field("private_segment_fixed_size") == 0, name
-        assert field("group_segment_fixed_size") == (512 if "top" in name else 0), name
-        assert field("next_free_vgpr") <= 128, name
-    spills = re.findall(r"\.name:\s+(\S*priority_\w+_kernel\S*)(?:(?!\.name:).)*?\.vgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(spills) == 8 and all(int(n) == 0 for _, n in spills), spills
-    sspills = re.findall(r"\.name:\s+(\S*priority_\w+_kernel\S*)(?:(?!\.name:).)*?\.sgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(sspills) == 8 and all(int(n) == 0 for _, n in sspills), sspills
+        assert field["private_segment_fixed_size"] == 0, name
+        assert field["group_segment_fixed_size"] == (512 if "top" in name else 0), name
+        assert field["next_free_vgpr"] <= 128, name
+    spills = engine_asm.spill_counts(r"\S*priority_\w+_kernel\S*")
+    assert len(spills) == 8 and all(n == 0 for _, n in spills), spills
+    sspills = engine_asm.spill_counts(r"\S*priority_\w+_kernel\S*", kind="sgpr")
+    assert len(sspills) == 8 and all(n == 0 for _, n in sspills), sspills
     for name, _ in kernels:
-        st = text.index("\n" + name + ":")
-        fn = text[st:text.index(".Lfunc_end", st)]
+        fn = engine_asm.function(name)
         writes = set(re.findall(r"^\s+(\w*(?:store|atomic)\w*)\s", fn, flags=re.M))
         allowed = {"global_store_dword", "global_store_dwordx2", "global_store_dwordx3", "global_store_dwordx4"}
         if "update" in name:

@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import engine_asm
 from replay_model import Ring, draws, philox4x32_10, sample, synthetic, umul64hi
 from test_episode_stats import _fake_cuda, _stub_env
 from test_gae import _struct_fields
-from test_snapshot_device import _function_body, _header_args
+from test_snapshot_device import _header_args
 
 B, D, T = 8, 13, 12
 
@@ -372,9 +373,9 @@ def test_the_status_message_of_a_refused_replay_call_is_reachable():
     assert re.search(r"constexpr uint32_t kStreamReplay = 3u;", inc)
     assert "kStreamReset = 0u, kStreamGoal = 1u, kStreamAction = 2u;" in open(os.path.join(build.CSRC, "sg_device.hpp")).read()
     for fn, n in (("void replay_commit_list_kernel(", 1), ("void replay_finish_kernel(", 2), ("void replay_sample_kernel(", 2)):
-        assert len(re.findall(r"\*status = kStatusReplay;", _function_body(inc, fn))) == n, fn
+        assert len(re.findall(r"\*status = kStatusReplay;", engine_asm.function_body(inc, fn))) == n, fn
     for sig in ("static int status_error(sg_env *e, const char *who)", 'extern "C" int sg_check_status(sg_env *e)'):
-        assert re.search(r"if \(st == kStatusReplay\)\s*return fail\(", _function_body(src, sig)), sig
+        assert re.search(r"if \(st == kStatusReplay\)\s*return fail\(", engine_asm.function_body(src, sig)), sig
     lib = open(build.build(), "rb").read()
     assert b"sg_replay_*_device: a ring without a matching header" in lib
     assert b"an earlier sg_replay_*_device call refused its input on the device" in lib
@@ -386,35 +387,23 @@ def test_the_new_kernels_build_for_gfx950_without_scratch():
     float64 operation of the return rounds on its own); every instruction that writes memory is a global_store_* of a byte, a
     dword or (the int64 index) two dwords -- nothing assumes more than the element's alignment -- except the one global atomic of
     the dense commit's reservation"""
-    import shutil
-    import subprocess
-    import tempfile
     from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
+    engine_asm.text()  # (skips without a compiler)
     lib = open(build.build(), "rb").read()
     for name in (b"sg_replay_bytes", b"sg_replay_begin_device", b"sg_replay_commit_device", b"sg_replay_sample_device",
                  b"replay_sample_kernel", b"replay_commit_list_kernel", b"replay_commit_dense_kernel", b"replay_finish_kernel"):
         assert name in lib
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        text = open(asm).read()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*replay_\w+_kernel\S*)\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    kernels = engine_asm.descriptors(r"\S*replay_\w+_kernel\S*")
     # begin, commit_list, dense_mark, commit_dense, finish, tick, sample<1 | 4 | 8 | 16>
     assert len(kernels) == 10, [k for k, _ in kernels]
-    for name, body in kernels:
-        field = lambda k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))  # noqa: E731
-        assert field("private_segment_fixed_size") == 0, name
-        assert field("group_segment_fixed_size") == (20 if "commit_dense" in name else 0), name
-        assert field("next_free_vgpr") <= 128, name
-    spills = re.findall(r"\.name:\s+(\S*replay_\w+_kernel\S*)(?:(?!\.name:).)*?\.vgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(spills) == 10 and all(int(n) == 0 for _, n in spills), spills
+    for name, field in kernels:
+        assert field["private_segment_fixed_size"] == 0, name
+        assert field["group_segment_fixed_size"] == (20 if "commit_dense" in name else 0), name
+        assert field["next_free_vgpr"] <= 128, name
+    spills = engine_asm.spill_counts(r"\S*replay_\w+_kernel\S*")
+    assert len(spills) == 10 and all(n == 0 for _, n in spills), spills
     for name, _ in kernels:
-        st = text.index("\n" + name + ":")
-        fn = text[st:text.index(".Lfunc_end", st)]
+        fn = engine_asm.function(name)
         writes = set(re.findall(r"^\s+(\w*(?:store|atomic)\w*)\s", fn, flags=re.M))
         allowed = {"global_store_dword", "global_store_byte", "global_store_dwordx2"}
         if "commit_dense" in name:

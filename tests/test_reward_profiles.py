@@ -102,40 +102,15 @@ def test_profiled_step_kernels_wait_for_memory_only_at_the_top_of_a_pass():
     the profile indices come with the subtile's LDS-DMA group and the table is in LDS, so behind the loop's group of
     global_load_lds at least 300 instructions follow without an `s_waitcnt vmcnt`.  Every new kernel: no spill, no scratch; the
     one-wave step kernels at two waves per SIMD and the wave-pair rollout kernels at most 256 registers."""
-    import re
-    import shutil
-    import subprocess
-    import tempfile
-    from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        lines = open(asm).read().splitlines()
-    starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\d+(goal|kepler)_step_profiled_kernelI\w*:", l)]
-    assert len(starts) == 8  # 2P / 3P / 4P x two steerings, Kepler x two steerings
-    for st in starts:
-        end = next(i for i in range(st, len(lines)) if lines[i].startswith(".Lfunc_end"))
-        ins = [l.split(";")[0].strip() for l in lines[st + 1:end]]
-        ins = [l for l in ins if l and not l.startswith(".") and not l.endswith(":")]
-        dma = [k for k, l in enumerate(ins) if l.startswith("global_load_lds")]
-        assert len(dma) >= 16, lines[st]  # the prologue's group and the loop's, each with the profile indices
-        last = dma[-1]
-        nxt = next((k for k in range(last + 1, len(ins)) if ins[k].startswith("s_waitcnt") and "vmcnt" in ins[k]), len(ins))
-        assert nxt - last >= 300, (lines[st], nxt - last)
-        first = next(k for k in dma if last - k < 120)
-        assert not any(l.startswith("s_waitcnt") and "vmcnt" in l for l in ins[first:last]), lines[st]
+    import engine_asm
+    # 2P / 3P / 4P x two steerings, Kepler x two steerings; the prologue's group and the loop's, each with the profile indices
+    engine_asm.assert_no_memory_wait_behind_dma(r"^_Z\d+(goal|kepler)_step_profiled_kernelI\w*:", n_kernels=8, min_dma=16)
     # resources of every profiled kernel, from the code object's kernel descriptors
-    text = "\n".join(lines)
-    kernels = re.findall(r"\.amdhsa_kernel (\S*profile\S*)\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    kernels = engine_asm.descriptors(r"\S*profile\S*")
     assert len(kernels) == 8 + 8 + 12 + 2 + 1  # one-wave and wave-pair step kernels, the rollout kernels, the index copy
-    for name, body in kernels:
-        field = lambda k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))  # noqa: E731
-        assert field("private_segment_fixed_size") == 0, name
+    for name, field in kernels:
+        assert field["private_segment_fixed_size"] == 0, name
         if ("_step_profiled_kernel" in name and "pair" not in name) or "_rollout_profiled_kernel" in name:
-            assert field("next_free_vgpr") <= 256, name
-    spills = re.findall(r"\.name:\s+(\S*profile\S*)(?:(?!\.name:).)*?\.vgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(spills) == 31 and all(int(n) == 0 for _, n in spills), spills
+            assert field["next_free_vgpr"] <= 256, name
+    spills = engine_asm.spill_counts(r"\S*profile\S*")
+    assert len(spills) == 31 and all(n == 0 for _, n in spills), spills

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import engine_asm
 from test_episode_stats import _fake_cuda, _stub_env
 
 ENV_ID = "GoalContinuous3P-v0"
@@ -153,16 +154,6 @@ def test_multi_device_front_ends_refuse_snapshots():
                 call()
 
 
-def _function_body(src, signature):
-    start = src.index(signature)
-    depth, k = 0, src.index("{", start)
-    for k in range(k, len(src)):
-        depth += {"{": 1, "}": -1}.get(src[k], 0)
-        if depth == 0:
-            return src[start:k + 1]
-    raise AssertionError(signature)
-
-
 def test_the_status_message_of_a_refused_restore_is_reachable():
     """the restore kernels set the status word to kStatusSnapshot; both readers of the word -- status_error (every later call)
     and sg_check_status (which clears it) -- have a message of their own for it, and the built library carries them"""
@@ -171,9 +162,9 @@ def test_the_status_message_of_a_refused_restore_is_reachable():
     code = int(re.search(r"constexpr int kStatusSnapshot = (\d+);", src).group(1))
     others = [int(v) for v in re.findall(r"constexpr int kStatus(?!Snapshot)\w+ = (\d+);", src)]
     assert code not in others and code > 3  # (1 .. 3: the rollout kernels' hand-off waits)
-    assert len(re.findall(r"\*status = kStatusSnapshot;", _function_body(src, "void restore_envs("))) == 2  # header, source index
+    assert len(re.findall(r"\*status = kStatusSnapshot;", engine_asm.function_body(src, "void restore_envs("))) == 2  # header, source index
     for sig in ("static int status_error(sg_env *e, const char *who)", 'extern "C" int sg_check_status(sg_env *e)'):
-        body = _function_body(src, sig)
+        body = engine_asm.function_body(src, sig)
         assert re.search(r"if \(st == kStatusSnapshot\)\s*return fail\(", body), sig
     lib = open(build.build(), "rb").read()
     assert b"sg_restore_device: a snapshot of another env id, batch size or configuration" in lib
@@ -184,35 +175,23 @@ def test_the_new_kernels_build_for_gfx950_without_scratch():
     """build() makes the library with the three entry points; the code object's kernel descriptors of snapshot_kernel and the
     four restore kernels: no scratch, no spill, no LDS, and few enough registers for full occupancy (<= 64 VGPRs: 8 waves per
     SIMD) -- these kernels only move bytes."""
-    import shutil
-    import subprocess
-    import tempfile
     from space_gym_amd import build
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
+    engine_asm.text()  # (skips without a compiler)
     lib = open(build.build(), "rb").read()
     for name in (b"sg_snapshot_bytes", b"sg_snapshot_device", b"sg_restore_device"):
         assert name in lib
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "sg.s")
-        flags = [f for f in build.flags() if f not in ("-shared", "-fPIC")]
-        subprocess.run([build.hipcc(), *flags, "-S", "--cuda-device-only", "-o", asm, os.path.join(build.CSRC, "sg_engine.hip")],
-                       check=True, capture_output=True, timeout=900)
-        text = open(asm).read()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*(?:snapshot_kernel|_restore_kernel)\S*)\n(.*?)\.end_amdhsa_kernel", text, flags=re.S)
+    kernels = engine_asm.descriptors(r"\S*(?:snapshot_kernel|_restore_kernel)\S*")
     assert len(kernels) == 5, [k for k, _ in kernels]  # snapshot_kernel, goal_restore_kernel<2|3|4>, kepler_restore_kernel
-    for name, body in kernels:
-        field = lambda k: int(re.search(r"\.amdhsa_" + k + r" (\d+)", body).group(1))  # noqa: E731
-        assert field("private_segment_fixed_size") == 0, name
-        assert field("group_segment_fixed_size") == 0, name
-        assert field("next_free_vgpr") <= 64, name
-    spills = re.findall(r"\.name:\s+(\S*(?:snapshot_kernel|_restore_kernel)\S*)(?:(?!\.name:).)*?\.vgpr_spill_count:\s+(\d+)", text, flags=re.S)
-    assert len(spills) == 5 and all(int(n) == 0 for _, n in spills), spills
+    for name, field in kernels:
+        assert field["private_segment_fixed_size"] == 0, name
+        assert field["group_segment_fixed_size"] == 0, name
+        assert field["next_free_vgpr"] <= 64, name
+    spills = engine_asm.spill_counts(r"\S*(?:snapshot_kernel|_restore_kernel)\S*")
+    assert len(spills) == 5 and all(n == 0 for _, n in spills), spills
     # every instruction of the new kernels that writes memory is a global_store_*: the columns, and the one-lane writes of the
     # header, the status word and the render epoch word alike
     for name, _ in kernels:
-        st = text.index("\n" + name + ":")
-        fn = text[st:text.index(".Lfunc_end", st)]
+        fn = engine_asm.function(name)
         writes = re.findall(r"^\s+(\w*(?:store|atomic)\w*)\s", fn, flags=re.M)  # (instructions are indented, labels are not)
         assert len(writes) >= 4 and all(w.startswith("global_store_") for w in writes), (name, sorted(set(writes)))
         # the 16-byte columns move as 16-byte loads and stores

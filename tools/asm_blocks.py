@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """Build aid (no GPU): static instruction counts per basic block of one kernel, from the device assembly
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-gpu-rdc -ffp-contract=on -I include -I space_gym_amd/csrc -S --cuda-device-only -o sg.s space_gym_amd/csrc/sg_engine.hip
-    python tools/asm_blocks.py sg.s 'goal_step_kernelILi3ELb0E'
+(build.device_asm(): compiled again only when a source is newer) or from an assembly file of one's own
+    python tools/asm_blocks.py [file.s] 'goal_step_kernelILi3ELb0E'
 """
+import os
 import re
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from space_gym_amd import build  # noqa: E402
+
 
 def main():
-    s = open(sys.argv[1]).read().splitlines()
-    pat = re.compile(r'^(_Z\w*' + sys.argv[2] + r'\w*):')
+    path, kernel = sys.argv[1:] if len(sys.argv) > 2 else (build.device_asm()[0], sys.argv[1])
+    s = open(path).read().splitlines()
+    pat = re.compile(r'^(_Z\w*' + kernel + r'\w*):')
     start = [i for i, l in enumerate(s) if pat.match(l)][0]
     end = next(i for i in range(start, len(s)) if s[i].startswith('.Lfunc_end'))
     blocks, cur = [], ['entry', []]

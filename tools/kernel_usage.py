@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build aid (no GPU): registers, spills, LDS and occupancy of every kernel of the library as the compiler reports them
-(hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
+(build.device_asm()'s resource remarks, compiled again only when a source is newer), one line per kernel.
 
     python tools/kernel_usage.py [substring ...]      only kernels whose demangled name contains every substring
 """
@@ -15,21 +15,7 @@ from space_gym_amd import build  # noqa: E402
 
 
 def main():
-    cmd = [build.hipcc(), *build.flags(("-Rpass-analysis=kernel-resource-usage",)), "-o", "/dev/null",
-           os.path.join(build.CSRC, "sg_engine.hip")]
-    err = subprocess.run(cmd, capture_output=True, text=True).stderr
-    rows, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: \s*(.+?)\s*\[-Rpass-analysis", line)
-        if not m:
-            continue
-        k, _, v = m.group(1).partition(":")
-        k, v = k.strip(), v.strip()
-        if k == "Function Name":
-            cur = {"name": v}
-            rows.append(cur)
-        elif cur is not None:
-            cur[k] = v
+    rows = build.resource_report(build.device_asm()[1])
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
     print("%-66s %5s %5s %7s %7s %8s %4s" % ("kernel", "VGPR", "SGPR", "Sspill", "Vspill", "LDS", "occ"))
     for r, n in zip(rows, names):

@@ -325,6 +325,49 @@ def test_other_configurations_equal_the_model(kw):
     _report(worst)
 
 
+@pytest.mark.parametrize("normalize_advantage", [True, False], ids=["normalized", "raw_advantage"])
+@pytest.mark.parametrize("env_id", [GOAL, DISCRETE])
+def test_indices_outside_the_rows_are_clamped_counted_and_contribute_nothing(env_id, normalize_advantage):
+    """5: indices outside the rows (the clamped, defined case of the contract) in four entries of the minibatch: counted in bad_rows,
+    their per-row g_logp / g_value exactly 0, and rows, statistics and gradients against the model on the same index within test 2's
+    tolerances; which way and how far outside is all the same to every output; without those entries bad_rows is 0"""
+    env, h, pol, _, batch, host = _rollout(env_id, 64, 2, "tanh")
+    n, rows_total = 200, K * B
+    kw = dict(KW, normalize_advantage=normalize_advantage)
+    index = _index(n, 61)
+    where = [0, 7, 131, 199]  # in both row tiles of R = 128
+
+    def run(idx):
+        rows = _row_outputs(len(idx))
+        grads, stats = env.ppo_grad_torch(h, batch, _dev(idx), rows=rows, **kw)
+        return _grads_np(grads), _np(stats)[0], dict(zip(rows, _np(*rows.values())))
+
+    bad = index.copy()
+    bad[where] = [-1, rows_total, -2 ** 40, 2 ** 40]
+    got, stats, r = run(bad)
+    what = (env_id, n, normalize_advantage, "bad index")
+    assert stats[9] == 4 and np.isfinite(stats).all(), (what, stats)
+    assert not r["g_logp"][where].any() and not r["g_value"][where].any() and r["g_logp"].any() and r["g_value"].any(), what
+    m64, m32 = ppo(pol, host, bad, **kw), ppo(pol, host, bad, dtype=np.float32, **kw)
+    assert m64["stats"][9] == 4
+    worst = []
+    _check_rows_and_stats(r, stats, m32, m64, kw, what, worst)
+    _check_grads(got, flat(m32), flat(m64), what, worst)
+    _report(worst)
+    # each entry stays on its side of the rows, so it is clamped to the same row: every output has the same bits
+    other = index.copy()
+    other[where] = [-7, rows_total + 5, np.iinfo(np.int64).min, np.iinfo(np.int64).max]
+    got2, stats2, r2 = run(other)
+    _assert_same_bits(got, got2, what)
+    _assert_same_bits(r, r2, what)
+    assert stats.tobytes() == stats2.tobytes(), (what, stats, stats2)
+    clean = np.delete(index, where)
+    got3, stats3, r3 = run(clean)
+    assert len(clean) == n - 4 and stats3[9] == 0 and np.isfinite(stats3).all(), (what, stats3)
+    assert any(got3[k].tobytes() != got[k].tobytes() for k in got)
+    env.check_status()
+
+
 def test_a_captured_update_replays_the_eager_results():
     """5: captured after a warm-up call that sizes the workspace; without one the call raises inside the capture and launches nothing"""
     import torch

@@ -997,6 +997,57 @@ int sg_ppo_population_grad_device(sg_env *env, const sg_policy *policy, int32_t 
  * rounded up to 8 bytes, double [members][Gadv][2], float [members][G][8]; 0 and an error message for an invalid policy, members or n */
 size_t sg_ppo_population_grad_workspace_bytes(sg_env *env, const sg_policy *policy, int32_t members, int64_t n);
 
+/* The parameter update: one Adam / AdamW step with global-norm gradient clipping for every member of a population (members = 1: a single
+ * net), each member with its own hyperparameters, independently of every other member.  The optimizer is elementwise over a table of
+ * tensors and knows nothing about nets: entry k is one parameter tensor stacked [members, numel], contiguous float32, with its gradient
+ * and its two moments in the same layout.  All device memory is the caller's; the gradients are READ ONLY (the clipped gradient is never
+ * written back).  tests/adam_model.py states every operation and its order in NumPy and is the contract; DESIGN section 26 has the kernels.
+ *   hyper   float32 DEVICE [members, 8], row m = (lr, beta1, beta2, eps, weight_decay, max_grad_norm, reserved, reserved) of member m.
+ *           Read by the kernels at every launch: a captured graph changes a learning rate by writing the tensor.  ITS VALUES ARE NOT
+ *           CHECKED (as member_coef above); a bad value affects that member only.
+ *   state   float64 DEVICE [members, 8], 8-byte aligned, row m = (steps, beta1_pow, beta2_pow, skipped, grad_norm, clip_scale, step_size,
+ *           applied).  The first four are the member's running state (a fresh member: 0, 1, 1, 0); the last four are what the most
+ *           recent call used, each a float32 value stored exactly (applied: 0 or 1), and are how the first launch hands the member's
+ *           constants to the second.
+ * Per member m, one call:
+ *   1. grad_norm = float32(sqrt(S)), S the float64 sum of the float64 squares of ALL of member m's gradient elements of the table (the
+ *      global norm over actor, critic and log_std together), summed in a fixed order: lane l of 1024 takes elements l, l + 1024, ...
+ *      of entry 0, then of entry 1, ...; then lane[i] += lane[i + s] for s = 512, 256, ..., 1.  No atomics.
+ *   2. clip_scale = float32(min(1, max_grad_norm / (grad_norm + 1e-6))), in float64, when 0 < max_grad_norm < inf (torch's
+ *      clip_grad_norm_); any other max_grad_norm (0, negative, inf, NaN) gives exactly 1, by the comparison.
+ *   3. grad_norm not finite (an inf or NaN anywhere in the member's gradient): the member's step is SKIPPED -- parameters, moments,
+ *      steps and the beta powers keep their bits, skipped goes up by one, clip_scale = step_size = applied = 0.
+ *   4. Otherwise, in float64 with each operation rounded: beta1_pow *= beta1, beta2_pow *= beta2 (running products: device pow is not
+ *      correctly rounded, and a product is right when a member's beta changes between steps), steps += 1,
+ *      step_size = float32(lr / (1 - beta1_pow)), bc2s = float32(sqrt(1 - beta2_pow)), applied = 1; and per element in float32, every
+ *      operation rounded on its own, 1 - beta and lr weight_decay formed in float32:
+ *          g' = g clip_scale;  m' = beta1 m + (1 - beta1) g';  v' = beta2 v + ((1 - beta2) g') g';
+ *          den = sqrt(v') / bc2s + eps;  p' = (p - (lr weight_decay) p) - (step_size m') / den
+ *      (decoupled weight decay, AdamW; weight_decay = 0 is Adam).  Float32 denormals are kept.
+ * Two launches: one workgroup per member for 1 .. 4's per-member part, then the elementwise update, which reads no state that its own
+ * launch writes.  Allocates nothing, never synchronises, hipGraph-capturable; the same inputs give the same bits.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): members outside 1 .. 65535; n_tensors outside 1 .. 32; a NULL tensors, or
+ * a NULL pointer in a table entry; numel < 1, or members x numel above 2^31 - 1; a NULL hyper or state; state not 8-byte aligned. */
+typedef struct sg_adam_tensor {
+    float *param;        /* [members, numel] */
+    const float *grad;   /* [members, numel]; read only.  sg_adam_exploit_device does not look at it (may be NULL there) */
+    float *exp_avg;      /* [members, numel]; zeros before the first step */
+    float *exp_avg_sq;   /* [members, numel]; zeros before the first step */
+    int64_t numel;       /* elements PER MEMBER */
+} sg_adam_tensor;
+int sg_adam_step_device(sg_env *env, int32_t members, int32_t n_tensors, const sg_adam_tensor *tensors, const float *hyper, double *state,
+                        void *hip_stream);
+/* PBT's exploit step with the optimizer state carried along.  src int32 DEVICE [members]: for every m with src[m] != m, member m's
+ * parameter, exp_avg and exp_avg_sq slices of every table entry and columns 0 .. 3 of its state row become those of member src[m].
+ * hyper is not touched: explore is the caller's write.  One launch, no staging buffer, race-free by this rule: a copy is performed only
+ * if its source is not itself a destination (src[src[m]] == src[m]) -- truncation selection (the bottom k copy the top k) always
+ * satisfies it.  A copy that breaks the rule, or whose src[m] is outside [0, members), is NOT PERFORMED (the test is made before any
+ * address is formed from src[m]) and is counted in refused_out (int32 DEVICE [1], may be NULL; written, not accumulated).
+ * Allocates nothing, never synchronises, hipGraph-capturable.  Refused as sg_adam_step_device refuses members, n_tensors and the table
+ * (grad aside); a NULL state or src; state not 8-byte aligned. */
+int sg_adam_exploit_device(sg_env *env, int32_t members, int32_t n_tensors, const sg_adam_tensor *tensors, double *state, const int32_t *src,
+                           int32_t *refused_out, void *hip_stream);
+
 /* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
  * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
  * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.

@@ -135,6 +135,11 @@ class SgPpoRows(C.Structure):
     _fields_ = [("logp", C.c_void_p), ("value", C.c_void_p), ("g_logp", C.c_void_p), ("g_value", C.c_void_p)]
 
 
+class SgAdamTensor(C.Structure):
+    """sg_adam_tensor (include/spacegym.h): one parameter tensor stacked [members, numel] with its gradient and its two moments"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64)]
+
+
 class SgQnet(C.Structure):
     """sg_qnet (include/spacegym.h): one or two Q critics on [obs | action] rows, parameters read where the learner keeps them"""
     _fields_ = [("struct_size", C.c_uint32), ("n_critics", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32),
@@ -289,6 +294,8 @@ SYMBOLS = {
     "sg_ppo_population_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, C.POINTER(SgPpoConfig), C.POINTER(SgPpoBatch), _vp, C.c_int64,
                                                 C.c_int64, C.POINTER(SgPolicyGrads), _vp, C.POINTER(SgPpoRows), _vp, C.c_size_t, _vp]),
     "sg_ppo_population_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64]),
+    "sg_adam_step_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(SgAdamTensor), _vp, _vp, _vp]),
+    "sg_adam_exploit_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(SgAdamTensor), _vp, _vp, _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

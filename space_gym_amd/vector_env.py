@@ -186,6 +186,17 @@ class PolicyPopulation:
         self.workspace = None  # population_grad_torch's partial sums: a uint8 tensor, grown on demand
 
 
+class AdamState:
+    """What adam_torch returns: the optimizer state of adam_step_torch over handle.tensors, which it keeps alive through the handle.
+    hyper float32 [P, 8] (env.adam_hyper_names) is read on the device at every call: write it to change a member's learning rate;
+    state float64 [P, 8] (env.adam_state_names); exp_avg / exp_avg_sq: float32 tensors shaped like handle.tensors; members = P."""
+
+    def __init__(self, handle, members, hyper, state, exp_avg, exp_avg_sq):
+        self.handle, self.members, self.hyper, self.state = handle, int(members), hyper, state
+        self.exp_avg, self.exp_avg_sq = tuple(exp_avg), tuple(exp_avg_sq)
+        self._table = None  # (the pointers it was made from, the sg_adam_tensor array)
+
+
 # per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id (Dqn: a continuous one)
 _NET_HANDLES = {Policy: ("policy", "policy_torch", "a = mean + exp(log_std) eps"), QNet: ("q", "q_torch", "the Q critics"),
                 SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor"), Dqn: ("dqn", "dqn_torch", "the DQN head Q(obs) -> 6"),
@@ -299,7 +310,7 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "squashed_sample_torch", "squashed_sample_raw_torch", "squashed_grad_torch", "dqn_torch", "dqn_act_torch", "rollout_dqn_torch",
                "dqn_evaluate_torch", "dqn_evaluate_raw_torch", "dqn_grad_torch", "policy_population_torch", "population_member_torch",
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
-               "population_grad_torch", "population_ppo_grad_torch")
+               "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch")
 
 
 class SpaceGymVectorEnv:
@@ -1663,7 +1674,8 @@ class SpaceGymVectorEnv:
         of contiguous float32 CUDA tensors, weight [P, out, in] and bias [P, out], shapes per member as policy_torch's; log_std
         float32 [P, 2] (continuous ids).  Member m owns the contiguous env block [m B / P, (m + 1) B / P) of the handle's B envs in
         population_act_torch / rollout_population_torch (P must divide B) and rows [m] of the [P, n, ...] tensors of the evaluate
-        and grad calls.  A PBT exploit step is W[loser].copy_(W[winner]) on the caller's tensors: the next call reads it."""
+        and grad calls.  A PBT exploit step is W[loser].copy_(W[winner]) on the caller's tensors: the next call reads it
+        (adam_exploit_torch does it for all members in one launch and carries the Adam state along)."""
         members = int(members)
         if not 1 <= members <= 65535:
             raise ValueError(f"members must be 1 .. 65535, got {members}")
@@ -1815,6 +1827,112 @@ class SpaceGymVectorEnv:
                                                          _ptr(stats), C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(),
                                                          self._stream()), "sg_ppo_population_grad_device")
         return out, stats
+
+    # ------------------------------------------------------------------ the parameter update: per-member Adam with clipping, PBT exploit
+    adam_hyper_names = ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm", "reserved", "reserved")  # AdamState.hyper [P, 8]
+    adam_state_names = ("steps", "beta1_pow", "beta2_pow", "skipped", "grad_norm", "clip_scale", "step_size", "applied")  # AdamState.state [P, 8]
+
+    def adam_torch(self, handle, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        """The optimizer state of adam_step_torch over handle.tensors: any handle of policy_torch, q_torch, squashed_policy_torch or
+        dqn_torch (P = 1) or of policy_population_torch (P = members).  Every hyperparameter is a scalar or a length-P sequence:
+        member m steps with its own learning rate, betas, eps, decoupled weight_decay (AdamW; 0 is Adam) and max_grad_norm (the
+        member's global-norm clip over all its gradients; None, inf or 0: off).  They are checked here; AdamState.hyper is READ ON THE
+        DEVICE at every call or graph replay, its later contents are not checked, and a bad value affects that member only -- PBT's
+        explore step, or a learning-rate schedule, is a write to that tensor.  The moments start at zero."""
+        import torch
+        if type(handle) not in _NET_HANDLES:
+            raise ValueError("handle: expected a handle of policy_torch, q_torch, squashed_policy_torch, dqn_torch or policy_population_torch")
+        P = handle.members if isinstance(handle, PolicyPopulation) else 1
+        for i, t in enumerate(handle.tensors):
+            self._check_tensor(f"handle.tensors[{i}]", t, torch.float32, t.shape)
+        hyper = np.zeros((P, len(self.adam_hyper_names)), np.float32)
+        betas = tuple(betas)
+        if len(betas) != 2:
+            raise ValueError("betas: expected (beta1, beta2)")
+        ok = {"lr": lambda v: np.isfinite(v) & (v >= 0), "beta1": lambda v: (v >= 0) & (v < 1), "beta2": lambda v: (v >= 0) & (v < 1),
+              "eps": lambda v: np.isfinite(v) & (v >= 0), "weight_decay": lambda v: np.isfinite(v) & (v >= 0), "max_grad_norm": lambda v: v >= 0}
+        scalar = max_grad_norm is None or np.ndim(max_grad_norm) == 0
+        clip = [float("inf") if x is None else x for x in ([max_grad_norm] if scalar else max_grad_norm)]  # (None: off, also inside a sequence)
+        given = (lr, betas[0], betas[1], eps, weight_decay, clip[0] if scalar else clip)
+        for c, (name, v) in enumerate(zip(self.adam_hyper_names, given)):
+            v = np.asarray(v, np.float64)
+            if v.shape not in ((), (P,)):
+                raise ValueError(f"{name}: expected a scalar or a sequence of {P} (one per member), got shape {v.shape}")
+            if not np.all(ok[name](v)):
+                raise ValueError(f"{name}: " + {"lr": "expected finite values >= 0", "beta1": "expected values in [0, 1)", "beta2": "expected values in [0, 1)",
+                                                "eps": "expected finite values >= 0", "weight_decay": "expected finite values >= 0",
+                                                "max_grad_norm": "expected values >= 0 (None, inf or 0: no clipping)"}[name] + f", got {v.tolist()}")
+            hyper[:, c] = v
+        dev = handle.tensors[0].device
+        state = np.zeros((P, len(self.adam_state_names)), np.float64)
+        state[:, 1:3] = 1.0
+        return AdamState(handle, P, torch.from_numpy(hyper).to(dev), torch.from_numpy(state).to(dev),
+                         tuple(torch.zeros_like(t) for t in handle.tensors), tuple(torch.zeros_like(t) for t in handle.tensors))
+
+    def _adam_state(self, opt):
+        if not isinstance(opt, AdamState):
+            raise ValueError("opt: expected the AdamState adam_torch returns")
+        import torch
+        self._check_tensor("opt.hyper", opt.hyper, torch.float32, (opt.members, len(self.adam_hyper_names)))
+        self._check_tensor("opt.state", opt.state, torch.float64, (opt.members, len(self.adam_state_names)))
+        return opt.members
+
+    def _adam_table(self, opt, flat):
+        """the sg_adam_tensor table over the handle's tensors whose entry of `flat` is not None (flat None: all of them, without
+        gradients), kept on the AdamState while the pointers stay the same"""
+        params = opt.handle.tensors
+        key = tuple(t.data_ptr() for t in (*params, *opt.exp_avg, *opt.exp_avg_sq)) + (
+            None if flat is None else tuple(None if g is None else g.data_ptr() for g in flat),)
+        if opt._table is None or opt._table[0] != key:
+            use = [k for k in range(len(params)) if flat is None or flat[k] is not None]
+            tab = (_native.SgAdamTensor * len(use))()
+            for row, k in zip(tab, use):
+                row.param, row.grad = params[k].data_ptr(), None if flat is None else flat[k].data_ptr()
+                row.exp_avg, row.exp_avg_sq = opt.exp_avg[k].data_ptr(), opt.exp_avg_sq[k].data_ptr()
+                row.numel = params[k].numel() // opt.members
+            opt._table = (key, tab)
+        return opt._table[1]
+
+    def adam_step_torch(self, opt, grads):
+        """One Adam / AdamW step of every member with its own row of opt.hyper (sg_adam_step_device: two launches, no host
+        synchronisation, nothing allocated, graph-capturable).  grads: the dict policy_grad_torch, ppo_grad_torch,
+        population_ppo_grad_torch, q_grad_torch, squashed_grad_torch or dqn_grad_torch returns; its tensors are read, never written.
+        A net whose gradients are None (a frozen critic) stays out of the norm and of the update.  Per member: the float32 l2 norm
+        over ALL its gradient elements, torch's clip_grad_norm_ coefficient for its max_grad_norm, and the update in float32 with
+        bias corrections from running beta products; a member whose norm is not finite is skipped and counted, the others step.
+        opt.state's columns (adam_state_names) report per member what the call used.  tests/adam_model.py is the arithmetic, bit for
+        bit.  Returns opt.state."""
+        import torch
+        P = self._adam_state(opt)
+        params = opt.handle.tensors
+        flat = list(_flat_grads(opt.handle, grads))
+        flat += [None] * (len(params) - len(flat))
+        if len(flat) != len(params):
+            raise ValueError(f"grads: {len(flat)} gradient tensors for the handle's {len(params)} parameter tensors")
+        if all(g is None for g in flat):
+            raise ValueError("grads: no tensor has a gradient")
+        for k, g in enumerate(flat):
+            if g is not None:
+                self._check_tensor(f"grads (tensor {k})", g, torch.float32, params[k].shape)
+        tab = self._adam_table(opt, flat)
+        self._ck(self._lib.sg_adam_step_device(self._h, P, len(tab), tab, _ptr(opt.hyper), _ptr(opt.state), self._stream()), "sg_adam_step_device")
+        return opt.state
+
+    def adam_exploit_torch(self, opt, src, refused=None):
+        """PBT's exploit step with the optimizer state carried along (sg_adam_exploit_device: one launch, graph-capturable).  src: int32
+        CUDA tensor [P]; for every m with src[m] != m, member m's parameters, both moments and its steps, beta powers and skipped count
+        become member src[m]'s.  opt.hyper is not touched: explore is the caller's write.  A copy is performed only if its source is not
+        itself a destination (src[src[m]] == src[m]) -- truncation selection always satisfies that -- and is in [0, P); the others are
+        not performed and are counted in refused (int32 CUDA tensor [1], written; optional)."""
+        import torch
+        P = self._adam_state(opt)
+        self._check_tensor("src", src, torch.int32, (P,))
+        if refused is not None:
+            self._check_tensor("refused", refused, torch.int32, (1,))
+        tab = self._adam_table(opt, None)
+        self._ck(self._lib.sg_adam_exploit_device(self._h, P, len(tab), tab, _ptr(opt.state), _ptr(src), _ptr(refused), self._stream()),
+                 "sg_adam_exploit_device")
+        return refused
 
     def population_evaluate_torch(self, pop, obs, action):
         """logp, entropy, value, each [P, n], of the stored rows under the CURRENT parameters, differentiable with respect to the

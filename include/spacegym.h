@@ -522,6 +522,70 @@ int sg_gae(sg_env *env, int32_t n_steps, const sg_gae_config *cfg, const float *
            const uint8_t *truncated_host, const float *value_host, const float *last_value_host,
            const float *terminal_value_dense_host, const sg_value_list *terminal_value_list, float *advantage_host, float *ret_host);
 
+/* Return targets with PER-GROUP discounts read on the device, for populations whose members explore gamma or lambda and for schedules
+ * inside a captured graph: GAE as above, and V-trace, the importance-corrected value target (Espeholt et al. 2018, IMPALA) for rollout
+ * rows that the policy being updated did not generate (another member's env block, a later epoch over the same rollout).  Device calls
+ * only; tests/returns_model.py is both recurrences in NumPy, bit for bit; DESIGN section 27 has the kernels.
+ *   discounts  float32 DEVICE [groups, 2], row g = (gamma, lambda) of group g.  groups >= 1 divides num_envs and env i reads row
+ *              i / (num_envs / groups): the population's block rule, so groups = members gives per-member discounts and groups = num_envs
+ *              per-env discounts.  Read by the kernel at every launch, each lane its two floats once: a captured graph changes a discount
+ *              by writing the tensor.  ITS VALUES ARE NOT CHECKED (as sg_adam_step_device's hyper): a NaN or a value outside [0, 1]
+ *              affects the envs of that group only.  Per env, in float64: gamma = (double) row[0], gl = (double) row[0] * (double) row[1]
+ *              (exact: two float32 factors), so a table whose rows are equal gives the bits of the scalar form at
+ *              gamma = (double)(float) g, lambda = (double)(float) l.
+ * sg_gae_groups_device is sg_gae_device -- its arguments, both terminal forms, bootstrap_truncated, a NULL value or last_value, its
+ * recurrence, its list check through the status word, its guarantees (caller's stream, one launch or two, nothing allocated, no
+ * synchronisation, hipGraph-capturable) -- with gamma and gl taken from the env's row.  groups >= 1 is required; cfg's gamma and lambda are
+ * not read, its bars are checked and not used.
+ * sg_vtrace_device adds
+ *   ratio         float32 [K, B]   the caller's exp(log pi(a | x) - log mu(a | x)) of the target policy pi over the behaviour policy mu;
+ *                                  NULL: on-policy, every ratio 1.  No exp runs on the device.
+ *   value         float32 [K, B]   required
+ *   vs            float32 [K, B]   output: the V-trace value targets
+ *   pg_advantage  float32 [K, B]   output: the policy gradient's advantage, min(pg_rho_bar, ratio) (r + gamma vs[t + 1] - V)
+ * and takes its discounts from the table (groups >= 1) or from cfg's gamma and lambda (groups = 0; gl = gamma * lambda rounded once on the
+ * host).  Per env i, in float64, every operation rounded on its own (no fused multiply-add):
+ *   acc = 0;  v_next = last_value[i] (0 if NULL)
+ *   for t = K - 1 .. 0:
+ *       rho = ratio[t, i] (1 if NULL)
+ *       rc = rho_bar < rho ? rho_bar : rho;  cc likewise with c_bar;  rp likewise with pg_rho_bar     -- a NaN ratio stays NaN
+ *       if done[t, i]:  term = the terminal value of (t, i) if truncated[t, i] and bootstrap_truncated and terminal values are given, else 0
+ *                       nv = term;    vs_next = term
+ *       else:           nv = v_next;  vs_next = v_next + acc
+ *       delta = rc * ((reward[t, i] + gamma * nv) - value[t, i])
+ *       acc   = done[t, i] ? delta : delta + (gl * cc) * acc                                           -- nothing crosses an episode boundary
+ *       vs[t, i] = (float) (acc + value[t, i])
+ *       pg_advantage[t, i] = (float) (rp * ((reward[t, i] + gamma * vs_next) - value[t, i]))
+ *       v_next = value[t, i]
+ * which is the paper's equation (1) with c_t = lambda min(c_bar, ratio).  With ratio NULL and the three bars >= 1, vs equals
+ * sg_gae_device's ret bit for bit.  The list form scatters into vs, where the scan reads each value before it overwrites it.
+ * Refused on the host (SG_ERR_INVALID, nothing enqueued): a null cfg, a wrong struct_size or reserved; n_steps < 1; a null reward, done,
+ * truncated or output; both terminal forms at once; groups < 0, groups that do not divide num_envs, groups >= 1 with a null discounts;
+ * with groups = 0, gamma or lambda outside [0, 1] or NaN (sg_gae_groups_device refuses groups = 0 itself); a bar that is <= 0 or NaN
+ * (+inf: no clipping); a null value (sg_vtrace_device). */
+typedef struct sg_returns_config {
+    uint32_t struct_size;         /* sizeof(sg_returns_config), set by sg_returns_config_init */
+    int32_t groups;               /* rows of discounts; 0: the scalars gamma and lambda below (sg_vtrace_device only) */
+    const float *discounts;       /* DEVICE float32 [groups, 2]: (gamma, lambda) per group; not read when groups = 0 */
+    double gamma;                 /* groups = 0: discount, in [0, 1] */
+    double lambda;                /* groups = 0: the trace's lambda, in [0, 1] */
+    int32_t bootstrap_truncated;  /* as sg_gae_config's */
+    double rho_bar;               /* V-trace: clips the ratio of the temporal difference; > 0, +inf allowed */
+    double c_bar;                 /* V-trace: clips the ratio of the trace; > 0, +inf allowed */
+    double pg_rho_bar;            /* V-trace: clips the ratio of pg_advantage; > 0, +inf allowed */
+    int32_t reserved;             /* 0 */
+} sg_returns_config;
+/* gamma 0.99, lambda 0.95, bootstrap_truncated 1, the three bars 1.0, groups 0 and a null discounts */
+void sg_returns_config_init(sg_returns_config *cfg);
+int sg_gae_groups_device(sg_env *env, int32_t n_steps, const sg_returns_config *cfg, const float *reward_dev, const uint8_t *done_dev,
+                         const uint8_t *truncated_dev, const float *value_dev, const float *last_value_dev,
+                         const float *terminal_value_dense_dev, const sg_value_list *terminal_value_list, float *advantage_dev,
+                         float *ret_dev, void *hip_stream);
+int sg_vtrace_device(sg_env *env, int32_t n_steps, const sg_returns_config *cfg, const float *reward_dev, const uint8_t *done_dev,
+                     const uint8_t *truncated_dev, const float *value_dev, const float *last_value_dev, const float *ratio_dev,
+                     const float *terminal_value_dense_dev, const sg_value_list *terminal_value_list, float *vs_dev,
+                     float *pg_advantage_dev, void *hip_stream);
+
 /* Replay ring with uniform n-step sampling -- what an off-policy learner (SAC, TD3: the learners the reference's README names) keeps
  * around the step: the last transitions (s, a, r, s', terminated), where s' of a finished step is the LAST observation of the episode
  * that ended (not the first one of the next episode, which auto-reset put into obs[t]) and a truncated step still bootstraps (SB3

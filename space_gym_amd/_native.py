@@ -66,6 +66,14 @@ class SgValueList(C.Structure):
     _fields_ = [("count", C.c_void_p), ("step_env", C.c_void_p), ("value", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class SgReturnsConfig(C.Structure):
+    """sg_returns_config (include/spacegym.h): sg_returns_config_init fills in gamma 0.99, lambda 0.95, bootstrap_truncated 1, the three
+    bars 1.0, groups 0"""
+    _fields_ = [("struct_size", C.c_uint32), ("groups", C.c_int32), ("discounts", C.c_void_p), ("gamma", C.c_double), ("lambda_", C.c_double),
+                ("bootstrap_truncated", C.c_int32), ("rho_bar", C.c_double), ("c_bar", C.c_double), ("pg_rho_bar", C.c_double),
+                ("reserved", C.c_int32)]
+
+
 class SgReplay(C.Structure):
     """sg_replay (include/spacegym.h): the members of a replay ring in device memory"""
     _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("term_capacity", C.c_uint32), ("reserved", C.c_uint32),
@@ -243,6 +251,11 @@ SYMBOLS = {
     "sg_gae_config_init": (None, [C.POINTER(SgGaeConfig)]),
     "sg_gae_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp, _vp]),
     "sg_gae": (C.c_int, [_vp, C.c_int32, C.POINTER(SgGaeConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp]),
+    "sg_returns_config_init": (None, [C.POINTER(SgReturnsConfig)]),
+    "sg_gae_groups_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgReturnsConfig), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp,
+                                       _vp]),
+    "sg_vtrace_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgReturnsConfig), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp,
+                                   _vp]),
     "sg_replay_bytes": (C.c_size_t, [_vp, C.c_int32, C.c_uint32, C.POINTER(C.c_size_t)]),
     "sg_replay_begin_device": (C.c_int, [_vp, C.POINTER(SgReplay), _vp, _vp]),
     "sg_replay_commit_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.c_int32, C.c_int32, C.c_int32, C.POINTER(SgTerminalList), _vp, _vp]),

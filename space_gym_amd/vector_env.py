@@ -1251,6 +1251,108 @@ class SpaceGymVectorEnv:
                                          ptr(out["returns"]), self._stream()), "sg_gae_device")
         return out["advantage"], out["returns"]
 
+    # ------------------------------------------------------------------ GAE and V-trace targets with per-group discounts
+    def _returns_call(self, reward, done, trunc, value, last_value, ratio, terminal_value, terminal, discounts, out, names):
+        """what gae_groups_torch and vtrace_torch check as gae_torch does; returns (K, the groups of `discounts` or 0, the value list or
+        None, the two outputs named `names` -- allocated when out is None)"""
+        import torch
+        if terminal_value is not None and terminal is not None:
+            raise ValueError("terminal_value and terminal: give the terminal values in one form")
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+            raise ValueError("reward: expected a CUDA tensor of shape (K, num_envs)")
+        K, B = int(reward.shape[0]), self.num_envs
+        if K < 1:
+            raise ValueError("reward: expected at least one step")
+        self._check_tensor("reward", reward, torch.float32, (K, B))
+        self._check_tensor("done", done, torch.uint8, (K, B))
+        self._check_tensor("trunc", trunc, torch.uint8, (K, B))
+        for name, t, shape in (("value", value, (K, B)), ("last_value", last_value, (B,)), ("ratio", ratio, (K, B)),
+                               ("terminal_value", terminal_value, (K, B))):
+            if t is not None:
+                self._check_tensor(name, t, torch.float32, shape)
+        groups = 0
+        if discounts is not None:
+            if not isinstance(discounts, torch.Tensor) or discounts.dim() != 2:
+                raise ValueError("discounts: expected a CUDA tensor of shape (groups, 2)")
+            groups = int(discounts.shape[0])
+            self._check_tensor("discounts", discounts, torch.float32, (groups, 2))
+            if groups < 1 or B % groups:
+                raise ValueError(f"discounts: its {groups} rows must divide num_envs = {B}")
+        vl = None
+        if terminal is not None:
+            cap = int(terminal["step_env"].shape[0])
+            if (not isinstance(terminal["count"], torch.Tensor) or terminal["count"].dtype not in (torch.int32, torch.uint32)
+                    or terminal["count"].numel() != 1):
+                raise ValueError("terminal['count']: expected one 32-bit integer")
+            self._check_tensor("terminal['count']", terminal["count"], terminal["count"].dtype, tuple(terminal["count"].shape))
+            self._check_tensor("terminal['step_env']", terminal["step_env"], torch.int32, (cap, 2))
+            self._check_tensor("terminal['value']", terminal["value"], torch.float32, (cap,))
+            vl = _native.SgValueList(terminal["count"].data_ptr(), terminal["step_env"].data_ptr(), terminal["value"].data_ptr(), cap)
+        if out is None:
+            out = {n: torch.empty((K, B), dtype=torch.float32, device=reward.device) for n in names}
+        else:
+            for n in names:
+                self._check_tensor(f"out['{n}']", out[n], torch.float32, (K, B))
+        return K, groups, vl, out
+
+    def gae_groups_torch(self, reward, done, trunc, discounts, value=None, last_value=None, terminal_value=None, terminal=None,
+                         bootstrap_truncated=True, out=None):
+        """gae_torch with per-group discounts read on the device (sg_gae_groups_device).  discounts: float32 device tensor [G, 2] of
+        (gamma, lambda) rows; G divides num_envs and env i uses row i // (num_envs // G) -- G = members gives a population per-member
+        discounts, G = num_envs per-env ones.  The kernel reads the tensor at every call or graph replay, so PBT's explore step or a
+        schedule inside a captured graph is a write to it; its values are NOT checked (a NaN or a value outside [0, 1] affects that
+        group's envs only).  Everything else is gae_torch's; equal rows give gae_torch's bits at gamma = float(float32(g)), lam
+        likewise.  Returns (advantage, returns); tests/returns_model.py states the arithmetic."""
+        if discounts is None:
+            raise ValueError("discounts: expected a CUDA tensor of shape (groups, 2)")
+        K, groups, vl, out = self._returns_call(reward, done, trunc, value, last_value, None, terminal_value, terminal, discounts, out,
+                                                ("advantage", "returns"))
+        cfg = _native.SgReturnsConfig(C.sizeof(_native.SgReturnsConfig), groups, discounts.data_ptr(), 0.99, 0.95, int(bool(bootstrap_truncated)),
+                                      1.0, 1.0, 1.0, 0)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_gae_groups_device(self._h, K, C.byref(cfg), ptr(reward), ptr(done), ptr(trunc), ptr(value), ptr(last_value),
+                                                ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(out["advantage"]),
+                                                ptr(out["returns"]), self._stream()), "sg_gae_groups_device")
+        return out["advantage"], out["returns"]
+
+    def vtrace_torch(self, reward, done, trunc, value, last_value=None, ratio=None, terminal_value=None, terminal=None, gamma=0.99, lam=1.0,
+                     discounts=None, rho_bar=1.0, c_bar=1.0, pg_rho_bar=None, bootstrap_truncated=True, out=None):
+        """V-trace value targets and policy-gradient advantages of a rollout (sg_vtrace_device; Espeholt et al. 2018): the
+        importance-corrected counterpart of gae_torch for rows the policy being updated did not generate -- another member's env block,
+        a later epoch over the same rollout.  ratio float32 [K, B]: exp(logp_target - logp_behaviour) of the action taken, formed by the
+        caller (None: on-policy, all ones; with the bars >= 1 vs is then gae_torch's returns bit for bit).  value is required.  The
+        discounts are the scalars gamma / lam, or -- discounts float32 [G, 2] given -- the rows of a device table as in gae_groups_torch
+        (gamma and lam are then not read).  rho_bar, c_bar, pg_rho_bar (None: rho_bar) clip the ratio of the temporal difference, of the
+        trace and of pg_advantage; each > 0, float("inf") for none.  reward / done / trunc / last_value / terminal_value / terminal /
+        bootstrap_truncated as gae_torch's.  out: dict vs / pg_advantage of float32 [K, B] (allocated when absent).  Returns
+        (vs, pg_advantage); tests/returns_model.py states the arithmetic."""
+        if pg_rho_bar is None:
+            pg_rho_bar = rho_bar
+        bars = dict(rho_bar=float(rho_bar), c_bar=float(c_bar), pg_rho_bar=float(pg_rho_bar))
+        for name, bar in bars.items():
+            if not bar > 0.0:
+                raise ValueError(f"{name} must be > 0, got {bar}")
+        if discounts is None:
+            checked = self._gae_config(gamma, lam, bootstrap_truncated)  # (gamma and lam in [0, 1])
+            gamma, lam = checked.gamma, checked.lambda_
+        else:
+            gamma, lam = 0.99, 0.95  # (not read)
+        if value is None:
+            raise ValueError("value: V-trace needs the values of the rollout's observations")
+        K, groups, vl, out = self._returns_call(reward, done, trunc, value, last_value, ratio, terminal_value, terminal, discounts, out,
+                                                ("vs", "pg_advantage"))
+        cfg = _native.SgReturnsConfig(C.sizeof(_native.SgReturnsConfig), groups, discounts.data_ptr() if groups else None, gamma, lam,
+                                      int(bool(bootstrap_truncated)), bars["rho_bar"], bars["c_bar"], bars["pg_rho_bar"], 0)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        self._ck(self._lib.sg_vtrace_device(self._h, K, C.byref(cfg), ptr(reward), ptr(done), ptr(trunc), ptr(value), ptr(last_value), ptr(ratio),
+                                            ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(out["vs"]),
+                                            ptr(out["pg_advantage"]), self._stream()), "sg_vtrace_device")
+        return out["vs"], out["pg_advantage"]
+
     # ------------------------------------------------------------------ what the net handles and their methods share
     def _mlp_layers(self, name, layers, fan_in, out, mlp, keep, members=None):
         """checks one net [(weight, bias), ...] of fan_in -> hidden -> ... -> out, writes its pointers into the sg_policy_mlp `mlp`,

@@ -697,6 +697,56 @@ typedef struct sg_replay_batch {
 int sg_replay_sample_device(sg_env *env, const sg_replay *ring, const sg_replay_sample_config *cfg, int64_t n,
                             const int64_t *index_in_dev, const sg_replay_batch *out, void *hip_stream);
 
+/* Fixed-length sequences from the replay ring: n columns of L = length consecutive steps of one env each, time-major, so that column
+ * j is one pseudo-env of an L-step rollout -- what V-trace (sg_vtrace_device), Retrace, Q(lambda), a multi-epoch PPO over old
+ * rollouts or a sequence model read.  With T, B, D, C, h = hdr.head, v = min(hdr.filled, T - 1) as above, first = (h - v) mod T the
+ * oldest valid slot and transition number u = q B + i the transition of env i at slot (first + q) mod T (sg_replay_sample_device's
+ * index_in, sg_priority_sample_device's index), a sequence of L in 1 .. T - 1 steps may start at q in [0, v - L + 1): its last step
+ * q + L - 1 is still a valid transition, so it never crosses the newest edge.  S = (v - L + 1) B.  For column j of the ring's call
+ * number c = hdr.sample_calls:
+ *   w      = philox4x32_10(key = seed, counter = (j lo, j hi, c, 8))        -- the engine's Philox, stream tag 8
+ *   u      = umul64hi(w0 | w1 << 32, S)                                     -- or index_in[j] when index_in is given
+ *   q, i   = u / B, u mod B;   p_k = (first + q + k) mod T,  k = 0 .. L - 1
+ *   obs[0, j]          = ring.obs[(p_0 - 1) mod T, i]
+ *   obs[k + 1, j]      = ring.obs[p_k, i]        -- what the rollout stored: after a done, the next episode's first observation
+ *   action[k, j], reward[k, j], done[k, j], trunc[k, j] = the ring's members at (p_k, i), bits unchanged
+ *   terminal_obs[k, j] = ring.term_obs[term_idx[p_k, i] mod C]  where done[p_k, i];  NOT WRITTEN elsewhere
+ *   extra_out[e][k, j] = extra_in[e][p_k, i]     -- e < n_extra <= 4
+ *   index[j]           = u
+ * Outputs: obs [L + 1, n, D], action [L, n, 2] (discrete ids: int32 [L, n]), reward, done, trunc [L, n]; with n = num_envs they go
+ * straight into sg_gae_device / sg_gae_groups_device / sg_vtrace_device, with terminal_value = V(terminal_obs) in the dense form.
+ * terminal_obs [L, n, D], index [n] and the extras may be NULL; the learner reads terminal_obs only where done.  extra_in[e] are
+ * caller-owned float32 [T, B] device arrays in the ring's slot layout (a closed-loop rollout's logp / value buffers are slices of
+ * them: they are how the behaviour log-prob reaches V-trace); the ring does not own them and commits do not touch them.
+ * One launch, plus the one lane that advances hdr.sample_calls (the ring's one counter, shared with sg_replay_sample_device), so a
+ * replayed captured call draws afresh and sees the ring grow.  The call allocates nothing, never synchronises and is capturable.
+ * Status code 8: no matching header, or v < L with n > 0 (nothing is written); an index_in[j] outside [0, S) (every row of column j
+ * of every output is left untouched).  n = 0 enqueues nothing.  Refused on the host (besides what every replay call refuses): a null
+ * cfg or a wrong struct_size, length outside 1 .. T - 1, n outside 0 .. 2^31 - 1, (length + 1) n > 2^31 - 1, a null out or a null
+ * obs, action, reward, done or trunc, n_extra outside 0 .. 4, a null extra_in[e] or extra_out[e] with e < n_extra.
+ * tests/sequence_model.py states all of this in NumPy, bit for bit. */
+typedef struct sg_replay_sequence_config {
+    uint32_t struct_size;  /* sizeof(sg_replay_sequence_config), set by sg_replay_sequence_config_init */
+    uint64_t seed;         /* Philox key of the draws */
+    int32_t length;        /* L: 1 .. T - 1 */
+    int32_t n_extra;       /* 0 .. 4 */
+} sg_replay_sequence_config;
+/* seed 0, length 1, n_extra 0 */
+void sg_replay_sequence_config_init(sg_replay_sequence_config *cfg);
+typedef struct sg_replay_sequences {
+    float *obs;                 /* [L + 1, n, D] */
+    void *action;               /* float32 [L, n, 2]; discrete ids: int32 [L, n] */
+    float *reward;              /* [L, n] */
+    uint8_t *done;              /* [L, n] */
+    uint8_t *trunc;             /* [L, n] */
+    float *terminal_obs;        /* [L, n, D], may be NULL; written only where done */
+    int64_t *index;             /* [n], may be NULL */
+    const float *extra_in[4];   /* [T, B] each; the first n_extra are read */
+    float *extra_out[4];        /* [L, n] each */
+} sg_replay_sequences;
+int sg_replay_sequence_device(sg_env *env, const sg_replay *ring, const sg_replay_sequence_config *cfg, int64_t n,
+                              const int64_t *index_in_dev, const sg_replay_sequences *out, void *hip_stream);
+
 /* Prioritized sampling from the replay ring (Schaul et al. 2016, proportional variant) with an exact integer sum tree.  A
  * caller-owned device object next to the ring holds one priority per cell c = p B + i (slot p, env i: by slot, so nothing moves when
  * the ring wraps) as an UNSIGNED FIXED-POINT INTEGER q with frac_bits fractional bits; every sum over them is a 64-bit integer.

@@ -93,6 +93,17 @@ class SgReplayBatch(C.Structure):
                 ("index", C.c_void_p)]
 
 
+class SgReplaySequenceConfig(C.Structure):
+    """sg_replay_sequence_config (include/spacegym.h): sg_replay_sequence_config_init fills in seed 0, length 1, n_extra 0"""
+    _fields_ = [("struct_size", C.c_uint32), ("seed", C.c_uint64), ("length", C.c_int32), ("n_extra", C.c_int32)]
+
+
+class SgReplaySequences(C.Structure):
+    """sg_replay_sequences (include/spacegym.h): the outputs of sg_replay_sequence_device and the extra columns it gathers"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("trunc", C.c_void_p),
+                ("terminal_obs", C.c_void_p), ("index", C.c_void_p), ("extra_in", C.c_void_p * 4), ("extra_out", C.c_void_p * 4)]
+
+
 class SgPriority(C.Structure):
     """sg_priority (include/spacegym.h): the members of the priorities of a replay ring in device memory"""
     _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("frac_bits", C.c_int32), ("reserved", C.c_uint32),
@@ -262,6 +273,9 @@ SYMBOLS = {
     "sg_replay_sample_config_init": (None, [C.POINTER(SgReplaySampleConfig)]),
     "sg_replay_sample_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplaySampleConfig), C.c_int64, _vp,
                                           C.POINTER(SgReplayBatch), _vp]),
+    "sg_replay_sequence_config_init": (None, [C.POINTER(SgReplaySequenceConfig)]),
+    "sg_replay_sequence_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplaySequenceConfig), C.c_int64, _vp,
+                                            C.POINTER(SgReplaySequences), _vp]),
     "sg_priority_bytes": (C.c_size_t, [_vp, C.c_int32, C.POINTER(C.c_size_t)]),
     "sg_priority_begin_device": (C.c_int, [_vp, C.POINTER(SgPriority), _vp]),
     "sg_priority_commit_device": (C.c_int, [_vp, C.POINTER(SgPriority), C.c_int32, C.c_int32, C.c_int32, _vp]),

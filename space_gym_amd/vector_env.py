@@ -2606,6 +2606,69 @@ class SpaceGymVectorEnv:
                                                    self._stream()), "sg_replay_sample_device")
         return out
 
+    # ------------------------------------------------------------------ fixed-length sequences from the replay ring
+    def replay_sample_sequences_torch(self, ring, n, length, seed=0, index=None, columns=None, out=None):
+        """n sequences of `length` consecutive steps of one env each, drawn uniformly with replacement among the starts whose last
+        step is still a valid transition (sg_replay_sequence_device: one launch; torch's current stream, no host synchronisation,
+        graph-capturable: a replayed call draws afresh).  Returns a dict of time-major tensors, column j one pseudo-env of an L-step
+        rollout: obs [L + 1, n, D], action [L, n, 2] (int32 [L, n]), reward, done, trunc [L, n], terminal_obs [L, n, D] (written
+        only where done; allocated as zeros), index (int64 [n], the transition number of each column's first step) and, with
+        columns=, `columns`: a list of [L, n] tensors.  With n == num_envs they go straight into gae_torch / gae_groups_torch /
+        vtrace_torch, with terminal_value = V(terminal_obs).  index: int64 [n] of first transitions in [0, len(ring) - (L - 1)
+        num_envs) to gather instead of drawing.  columns: up to four caller-owned float32 [T, B] tensors in the ring's slot layout
+        (e.g. the logp and value a closed-loop rollout wrote next to ring.rows(K)), gathered like the reward.  out: such a dict to
+        write into (terminal_obs, index and columns optional).  tests/sequence_model.py states the arithmetic."""
+        import torch
+        r = self._replay_arg(ring)
+        n, L, seed = int(n), int(length), int(seed)
+        T, B, D = ring.steps, self.num_envs, self.obs_dim
+        held = len(ring) // B
+        if not 0 <= n <= 2 ** 31 - 1:
+            raise ValueError(f"n: 0 .. 2^31 - 1 expected, got {n}")
+        if not 1 <= L <= T - 1:
+            raise ValueError(f"length: 1 .. {T - 1} expected for a ring of {T} slots, got {L}")
+        if L > held:
+            raise ValueError(f"length: {L} steps asked for, the ring holds {held} steps per env")
+        if (L + 1) * n > 2 ** 31 - 1:
+            raise ValueError(f"(length + 1) * n = {(L + 1) * n}: at most 2^31 - 1 (rows are addressed by 32 bits)")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed: an unsigned 64-bit integer expected, got {seed}")
+        if index is not None:
+            self._check_tensor("index", index, torch.int64, (n,))
+        columns = list(columns) if columns is not None else []
+        if len(columns) > 4:
+            raise ValueError(f"columns: at most 4 expected, got {len(columns)}")
+        for e, col in enumerate(columns):
+            self._check_tensor(f"columns[{e}]", col, torch.float32, (T, B))
+        spec = dict(obs=(torch.float32, (L + 1, n, D)), action=(torch.int32, (L, n)) if self.discrete else (torch.float32, (L, n, 2)),
+                    reward=(torch.float32, (L, n)), done=(torch.uint8, (L, n)), trunc=(torch.uint8, (L, n)),
+                    terminal_obs=(torch.float32, (L, n, D)), index=(torch.int64, (n,)))
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = {k: (torch.zeros if k == "terminal_obs" else torch.empty)(shape, dtype=dtype, device=dev)
+                   for k, (dtype, shape) in spec.items()}
+            if columns:
+                out["columns"] = [torch.empty((L, n), dtype=torch.float32, device=dev) for _ in columns]
+        else:
+            for k, (dtype, shape) in spec.items():
+                if k in out or k not in ("terminal_obs", "index"):
+                    self._check_tensor(f"out['{k}']", out[k], dtype, shape)
+            if columns:
+                if "columns" not in out:
+                    out["columns"] = [torch.empty((L, n), dtype=torch.float32, device=torch.device("cuda", self.device)) for _ in columns]
+                elif len(out["columns"]) != len(columns):
+                    raise ValueError(f"out['columns']: {len(columns)} tensors expected, got {len(out['columns'])}")
+                for e, col in enumerate(out["columns"]):
+                    self._check_tensor(f"out['columns'][{e}]", col, torch.float32, (L, n))
+        cfg = _native.SgReplaySequenceConfig(C.sizeof(_native.SgReplaySequenceConfig), seed, L, len(columns))
+        seqs = _native.SgReplaySequences(*(out[k].data_ptr() if k in out else None for k in spec))
+        for e, col in enumerate(columns):
+            seqs.extra_in[e], seqs.extra_out[e] = col.data_ptr(), out["columns"][e].data_ptr()
+        self._ck(self._lib.sg_replay_sequence_device(self._h, C.byref(r), C.byref(cfg), n,
+                                                     C.c_void_p(index.data_ptr()) if index is not None else None, C.byref(seqs),
+                                                     self._stream()), "sg_replay_sequence_device")
+        return out
+
     # ------------------------------------------------------------------ prioritized sampling with an exact integer sum tree
     def replay_priority_torch(self, ring, frac_bits=16):
         """The priorities of `ring` in device memory (ReplayPriority): one unsigned fixed-point integer with frac_bits fractional

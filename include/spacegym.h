@@ -1162,6 +1162,87 @@ int sg_adam_step_device(sg_env *env, int32_t members, int32_t n_tensors, const s
 int sg_adam_exploit_device(sg_env *env, int32_t members, int32_t n_tensors, const sg_adam_tensor *tensors, double *state, const int32_t *src,
                            int32_t *refused_out, void *hip_stream);
 
+/* The rest of a PBT generation on the device: member fitness from the rows a closed-loop rollout wrote, truncation selection, and
+ * explore.  With them a generation -- K closed-loop steps, returns, update, Adam, fitness, select, exploit, explore -- is one graph
+ * replay without a host synchronisation.  None of the calls reads the handle's env state: they depend on their arguments and on
+ * num_envs = B.  Every call takes the stream, allocates nothing, never synchronises, is hipGraph-capturable and uses no atomics; the
+ * same inputs give the same bits.  members = P is 1 .. 256 everywhere.  tests/pbt_model.py states every rule below in NumPy and is the
+ * contract; DESIGN section 29 has the kernels.
+ *
+ * FITNESS.  P must divide B; member m owns the envs [m E, (m + 1) E), E = B / P (the block rule of the population calls).
+ *   reward      float32 DEVICE [n_steps, B], done uint8 DEVICE [n_steps, B]: rows as a rollout wrote them, any n_steps >= 1; done
+ *               includes truncations.  THE VALUES OF reward ARE NOT CHECKED: a NaN stays within its env's member.
+ *   env_return  float64 DEVICE [B], env_length int32 DEVICE [B]: the running return and length of every env's unfinished episode,
+ *               read and written back, so that an episode may span calls (zeros before the first).
+ *   table       float64 DEVICE [P, 8], 8-byte aligned, row m = (episodes, return_sum, length_sum, return_sq_sum, return_max, return_min,
+ *               fitness, reserved) over the episodes member m's envs finished since the row was cleared.
+ * Pass 1, one lane per env, rows walked forward in t: run = run + (double) r in float64, each operation rounded on its own;
+ * len += 1; at done, in this order, cnt += 1, s += run, l += len, q += run run, mx = fmax(mx, run), mn = fmin(mn, run), then
+ * run = 0, len = 0 (identities 0, 0, 0, 0, -inf, +inf; fmax / fmin return the other operand of a NaN).  Pass 2: the per-env values
+ * of a member are reduced in chunks of 256 consecutive envs of its block, lanes past E holding the identities, by the fixed tree
+ * x[l] = x[l] (+) x[l + s] for s = 128, 64, ..., 1; one lane per member combines the chunk results in ascending order, starting
+ * from chunk 0's, then combines that window onto the table row (add, add, add, add, max, min) and writes
+ * fitness = return_sum / episodes when episodes >= 1, else NaN.  reserved is left alone.  The order is a function of (B, P) only.
+ * Two launches.  workspace: at least sg_pbt_fitness_workspace_bytes(env, members) bytes of device memory, 8-byte aligned, any content.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): members outside 1 .. 256 or not dividing num_envs; n_steps < 1; a null
+ * reward, done, env_return, env_length or table; table or env_return not 8-byte aligned; a null, short or misaligned workspace. */
+int sg_pbt_fitness_device(sg_env *env, int32_t members, int32_t n_steps, const float *reward, const uint8_t *done, double *env_return,
+                          int32_t *env_length, double *table, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_pbt_fitness_device needs: double [members][ceil(E / 256)][6]; 0 and an error message for invalid members */
+size_t sg_pbt_fitness_workspace_bytes(sg_env *env, int32_t members);
+/* Table rows back to (0, 0, 0, 0, -inf, +inf, NaN, 0).  src NULL: every row.  src int32 DEVICE [members], as sg_pbt_select_device
+ * wrote it: the rows with src[m] != m, the members that were replaced.  The per-env running values are not touched.  One launch.
+ * Refused: members outside 1 .. 256; a null table or one not 8-byte aligned. */
+int sg_pbt_fitness_clear_device(sg_env *env, int32_t members, double *table, const int32_t *src, void *hip_stream);
+
+/* SELECTION (truncation selection).  fitness float64 DEVICE, member m's value at fitness[m fitness_stride] (fitness_stride in
+ * elements, >= 1: 8 reads the table's fitness column in place); ready uint8 DEVICE [members] or NULL.  Member m TAKES PART if and only
+ * if ready[m] != 0 (or ready is NULL) and fitness[m] is not NaN; r is the number taking part.  k is the host's
+ * floor(fraction members), 0 <= k <= members / 2; the kernel uses k_eff = min(k, r / 2) (integer division).
+ *   rank[m] = #{ j taking part : f_j > f_m or (f_j == f_m and j < m) }: all pairs are compared, so it is exact; infinities compare
+ *   as floats do.  The top members are those with rank < k_eff, the bottom members those with rank >= r - k_eff.
+ * Each bottom member m draws one Philox block, key = seed, counter = (m, step lo, step hi, 9) -- stream tag 9, after the sequence
+ * sampler's 8 -- and src_out[m] is the member whose rank is floor(o0 k_eff / 2^32).  Every other member, taking part or not, gets
+ * src_out[m] = m.  So src_out[src_out[m]] == src_out[m] by construction: sg_adam_exploit_device refuses nothing of it.
+ *   src_out    int32 DEVICE [members]
+ *   rank_out   int32 DEVICE [members], may be NULL; -1 for the members not taking part
+ *   count_out  int32 DEVICE [2], may be NULL: (copies, k_eff)
+ *   step_dev   int64 DEVICE [1], may be NULL: its value is added to step (a 64-bit sum) by the kernel, so a captured graph draws
+ *              afresh when the caller bumps it inside the graph.
+ * One launch of one workgroup.  Refused: members outside 1 .. 256; a null fitness or src_out; fitness not 8-byte aligned;
+ * fitness_stride < 1; k outside 0 .. members / 2. */
+int sg_pbt_select_device(sg_env *env, int32_t members, const double *fitness, int64_t fitness_stride, const uint8_t *ready, int32_t k,
+                         uint64_t seed, uint64_t step, const int64_t *step_dev, int32_t *src_out, int32_t *rank_out, int32_t *count_out,
+                         void *hip_stream);
+
+/* EXPLORE.  One column of a float32 DEVICE tensor [members, C] of hyperparameters -- sg_adam_step_device's hyper, the PPO member_coef,
+ * a discounts table with one group per member, or any tensor of the caller's: data points at the column's element of row 0, stride
+ * is C.  For every m with src[m] != m, src[m] in [0, members) and src[src[m]] == src[m] (sg_adam_exploit_device's rule), and every
+ * column c = 0, 1, ...:
+ *   v = data[src[m] stride];  one Philox block, key = seed, counter = ((c << 16) | m, step lo, step hi, 10) -- stream tag 10;
+ *   f = (o0 >> 31) ? up : down;
+ *   SG_PBT_COPY: x = v;   SG_PBT_SCALE: x = v f;   SG_PBT_SCALE_COMPLEMENT: x = 1 - (1 - v) f   (gamma, lambda, beta: the distance
+ *   to 1 is scaled); every float32 operation rounded on its own; data[m stride] = fminf(fmaxf(x, lo), hi).
+ * A copy that the rule refuses is not made and is counted in refused_out (int32 DEVICE [1], may be NULL; written, not accumulated).
+ * Sources are never destinations, so no element is read and written in one launch; members with src[m] == m keep their bits.
+ * step_dev as above.  One launch of one workgroup; the columns travel by value.
+ * Refused: members outside 1 .. 256; a null src or columns; n_columns outside 1 .. 16; in a column, a null data, stride < 1, an
+ * unknown mode, a NaN down, up, lo or hi, or lo > hi. */
+#define SG_PBT_COPY 0
+#define SG_PBT_SCALE 1
+#define SG_PBT_SCALE_COMPLEMENT 2
+typedef struct sg_pbt_column {
+    float *data;      /* the column's element of member 0 */
+    int64_t stride;   /* elements between two members' rows */
+    int32_t mode;     /* SG_PBT_COPY / SG_PBT_SCALE / SG_PBT_SCALE_COMPLEMENT */
+    float down;       /* the factor drawn with probability 1/2 (0.8) */
+    float up;         /* the other one (1.25) */
+    float lo;         /* the clamp; -inf: none */
+    float hi;         /* +inf: none */
+} sg_pbt_column;
+int sg_pbt_explore_device(sg_env *env, int32_t members, const int32_t *src, int32_t n_columns, const sg_pbt_column *columns, uint64_t seed,
+                          uint64_t step, const int64_t *step_dev, int32_t *refused_out, void *hip_stream);
+
 /* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
  * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
  * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.

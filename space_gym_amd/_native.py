@@ -159,6 +159,12 @@ class SgAdamTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64)]
 
 
+class SgPbtColumn(C.Structure):
+    """sg_pbt_column (include/spacegym.h): one hyperparameter column of a float32 [members, C] tensor and how explore perturbs it"""
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int64), ("mode", C.c_int32), ("down", C.c_float), ("up", C.c_float), ("lo", C.c_float),
+                ("hi", C.c_float)]
+
+
 class SgQnet(C.Structure):
     """sg_qnet (include/spacegym.h): one or two Q critics on [obs | action] rows, parameters read where the learner keeps them"""
     _fields_ = [("struct_size", C.c_uint32), ("n_critics", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32),
@@ -323,6 +329,11 @@ SYMBOLS = {
     "sg_ppo_population_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgPolicy), C.c_int32, C.c_int64]),
     "sg_adam_step_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(SgAdamTensor), _vp, _vp, _vp]),
     "sg_adam_exploit_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(SgAdamTensor), _vp, _vp, _vp, _vp]),
+    "sg_pbt_fitness_device": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "sg_pbt_fitness_workspace_bytes": (C.c_size_t, [_vp, C.c_int32]),
+    "sg_pbt_fitness_clear_device": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
+    "sg_pbt_select_device": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "sg_pbt_explore_device": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, C.POINTER(SgPbtColumn), C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

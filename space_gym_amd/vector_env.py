@@ -29,6 +29,7 @@ Rendering (`render=True` / `render=dict(...)`, `set_render`): `render(mode="rgb_
 (gym_space/rendering.py) for chosen envs, drawn on the device -- `render()` (NumPy) and `render_torch()` (device tensor).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -197,6 +198,19 @@ class AdamState:
         self._table = None  # (the pointers it was made from, the sg_adam_tensor array)
 
 
+class PbtFitness:
+    """What pbt_fitness_torch returns: the running return and length of every env's unfinished episode (env_return float64 [B],
+    env_length int32 [B]), the per-member table float64 [P, 8] (env.pbt_fitness_names) over the episodes finished since a row was
+    cleared, and the workspace of pbt_fitness_update_torch; members = P.  fitness is the table's column 6, a view."""
+
+    def __init__(self, members, env_return, env_length, table, workspace):
+        self.members, self.env_return, self.env_length, self.table, self.workspace = int(members), env_return, env_length, table, workspace
+
+    @property
+    def fitness(self):
+        return self.table[:, 6]
+
+
 # per handle class: the argument's name, the method that makes the handle, and what cannot serve a discrete id (Dqn: a continuous one)
 _NET_HANDLES = {Policy: ("policy", "policy_torch", "a = mean + exp(log_std) eps"), QNet: ("q", "q_torch", "the Q critics"),
                 SquashedPolicy: ("sp", "squashed_policy_torch", "the squashed Gaussian actor"), Dqn: ("dqn", "dqn_torch", "the DQN head Q(obs) -> 6"),
@@ -310,7 +324,8 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "squashed_sample_torch", "squashed_sample_raw_torch", "squashed_grad_torch", "dqn_torch", "dqn_act_torch", "rollout_dqn_torch",
                "dqn_evaluate_torch", "dqn_evaluate_raw_torch", "dqn_grad_torch", "policy_population_torch", "population_member_torch",
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
-               "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch")
+               "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
+               "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch")
 
 
 class SpaceGymVectorEnv:
@@ -2034,6 +2049,167 @@ class SpaceGymVectorEnv:
         tab = self._adam_table(opt, None)
         self._ck(self._lib.sg_adam_exploit_device(self._h, P, len(tab), tab, _ptr(opt.state), _ptr(src), _ptr(refused), self._stream()),
                  "sg_adam_exploit_device")
+        return refused
+
+    # ------------------------------------------------------------------ the rest of a PBT generation: member fitness, selection, explore
+    pbt_fitness_names = ("episodes", "return_sum", "length_sum", "return_sq_sum", "return_max", "return_min", "fitness", "reserved")  # PbtFitness.table [P, 8]
+    pbt_max_members, pbt_max_columns = 256, 16
+    pbt_modes = {"copy": 0, "scale": 1, "scale_complement": 2}  # SG_PBT_COPY / SG_PBT_SCALE / SG_PBT_SCALE_COMPLEMENT
+
+    def _pbt_members(self, members, divide=False):
+        members = int(members)
+        if not 1 <= members <= self.pbt_max_members:
+            raise ValueError(f"members must be 1 .. {self.pbt_max_members}, got {members}")
+        if divide and self.num_envs % members:
+            raise ValueError(f"members: {members} does not divide num_envs = {self.num_envs} (member m owns the envs [m B / P, (m + 1) B / P))")
+        return members
+
+    def _pbt_fitness(self, fit):
+        import torch
+        if not isinstance(fit, PbtFitness):
+            raise ValueError("fit: expected the PbtFitness pbt_fitness_torch returns")
+        P = self._pbt_members(fit.members, divide=True)
+        self._check_tensor("fit.env_return", fit.env_return, torch.float64, (self.num_envs,))
+        self._check_tensor("fit.env_length", fit.env_length, torch.int32, (self.num_envs,))
+        self._check_tensor("fit.table", fit.table, torch.float64, (P, len(self.pbt_fitness_names)))
+        return P
+
+    def _pbt_step_dev(self, step_dev):
+        import torch
+        if step_dev is not None:
+            self._check_tensor("step_dev", step_dev, torch.int64, (1,))
+        return _ptr(step_dev)
+
+    def pbt_fitness_torch(self, members):
+        """The fitness state of a population of `members` = P (1 .. 256, dividing num_envs; member m owns the envs
+        [m B / P, (m + 1) B / P), as in rollout_population_torch): zero running returns and lengths, a cleared table, the workspace."""
+        import torch
+        P = self._pbt_members(members, divide=True)
+        need = int(self._lib.sg_pbt_fitness_workspace_bytes(self._h, P))
+        if need == 0:
+            self._ck(-1, "sg_pbt_fitness_workspace_bytes")
+        dev = torch.device("cuda", self.device)
+        table = torch.zeros((P, len(self.pbt_fitness_names)), dtype=torch.float64, device=dev)
+        table[:, 4], table[:, 5], table[:, 6] = float("-inf"), float("inf"), float("nan")
+        return PbtFitness(P, torch.zeros(self.num_envs, dtype=torch.float64, device=dev), torch.zeros(self.num_envs, dtype=torch.int32, device=dev),
+                          table, torch.empty(need // 8, dtype=torch.float64, device=dev))
+
+    def pbt_fitness_update_torch(self, fit, reward, done):
+        """Adds the episodes that finished inside the rows reward float32 [K, B], done uint8 / bool [K, B] (any K >= 1; as a rollout
+        wrote them, truncations included) to every member's row of fit.table, and carries every env's unfinished episode on in
+        fit.env_return / fit.env_length, so that episodes span calls (sg_pbt_fitness_device: two launches, no host synchronisation,
+        nothing allocated, graph-capturable).  Returns in float64, summed in a fixed order that depends on (B, P) only;
+        fitness = return_sum / episodes, NaN while a member has finished no episode.  tests/pbt_model.py is the arithmetic, bit for
+        bit.  The values of reward are not checked: a NaN stays within its env's member.  Returns fit.table."""
+        import torch
+        P = self._pbt_fitness(fit)
+        if not (isinstance(reward, torch.Tensor) and reward.dim() == 2 and reward.shape[0] >= 1):
+            raise ValueError("reward: expected a float32 CUDA tensor [K, num_envs] with K >= 1")
+        K = int(reward.shape[0])
+        self._check_tensor("reward", reward, torch.float32, (K, self.num_envs))
+        if isinstance(done, torch.Tensor) and done.dtype == torch.bool:
+            done = done.view(torch.uint8)  # (same bytes: no copy)
+        self._check_tensor("done", done, torch.uint8, (K, self.num_envs))
+        ws = fit.workspace
+        if not (isinstance(ws, torch.Tensor) and ws.dtype == torch.float64 and ws.dim() == 1):
+            raise ValueError("fit.workspace: expected the float64 tensor pbt_fitness_torch made")
+        self._check_tensor("fit.workspace", ws, torch.float64, ws.shape)
+        self._ck(self._lib.sg_pbt_fitness_device(self._h, P, K, _ptr(reward), _ptr(done), _ptr(fit.env_return), _ptr(fit.env_length),
+                                                 _ptr(fit.table), _ptr(ws), ws.numel() * 8, self._stream()), "sg_pbt_fitness_device")
+        return fit.table
+
+    def pbt_fitness_clear_torch(self, fit, src=None):
+        """Starts a new fitness window: table rows back to the identities and fitness to NaN (sg_pbt_fitness_clear_device: one launch,
+        graph-capturable).  src None: every row; src (int32 [P], as pbt_select_torch wrote it): the rows of the members that were
+        replaced, src[m] != m.  The running returns of unfinished episodes are left alone.  Returns fit.table."""
+        import torch
+        P = self._pbt_fitness(fit)
+        if src is not None:
+            self._check_tensor("src", src, torch.int32, (P,))
+        self._ck(self._lib.sg_pbt_fitness_clear_device(self._h, P, _ptr(fit.table), _ptr(src), self._stream()), "sg_pbt_fitness_clear_device")
+        return fit.table
+
+    def pbt_select_torch(self, fitness, ready=None, fraction=0.2, seed=0, step=0, step_dev=None, out=None, rank=None, count=None):
+        """Truncation selection on the device (sg_pbt_select_device: one launch, graph-capturable): src int32 [P] for
+        adam_exploit_torch, pbt_explore_torch and pbt_fitness_clear_torch.  fitness: float64 CUDA tensor [P], possibly a strided view
+        such as fit.table[:, 6]; ready: uint8 / bool [P], optional.  Member m takes part iff it is ready and its fitness is not NaN;
+        with r taking part and k_eff = min(floor(fraction P), r // 2), each of the k_eff worst draws one of the k_eff best (ties go to
+        the lower index; Philox keyed by seed, counter (m, step)) and every other member keeps itself, so src[src[m]] == src[m].
+        step_dev: int64 CUDA tensor [1] added to step on the device -- bump it inside a captured graph and every replay draws afresh.
+        rank: int32 [P], receives every member's rank (-1: not taking part); count: int32 [2], receives (copies, k_eff).  Returns src
+        (`out` if given)."""
+        import torch
+        if not (isinstance(fitness, torch.Tensor) and fitness.dim() == 1 and fitness.dtype == torch.float64):
+            raise ValueError("fitness: expected a float64 CUDA tensor [members] (a strided view such as fit.table[:, 6] will do)")
+        P = self._pbt_members(fitness.shape[0])
+        if not (fitness.is_cuda and fitness.device.index == self.device):
+            raise ValueError(f"fitness: expected a CUDA tensor on device {self.device}")
+        stride = int(fitness.stride(0)) if P > 1 else 1
+        if stride < 1:
+            raise ValueError(f"fitness: expected a positive stride, got {stride}")
+        if ready is not None:
+            if isinstance(ready, torch.Tensor) and ready.dtype == torch.bool:
+                ready = ready.view(torch.uint8)
+            self._check_tensor("ready", ready, torch.uint8, (P,))
+        fraction = float(fraction)
+        if not 0.0 < fraction <= 0.5:
+            raise ValueError(f"fraction: expected a value in (0, 0.5], got {fraction}")
+        ptr_step = self._pbt_step_dev(step_dev)
+        for name, t, n in (("out", out, P), ("rank", rank, P), ("count", count, 2)):
+            if t is not None:
+                self._check_tensor(name, t, torch.int32, (n,))
+        src = torch.empty(P, dtype=torch.int32, device=fitness.device) if out is None else out
+        self._ck(self._lib.sg_pbt_select_device(self._h, P, _ptr(fitness), stride, _ptr(ready), int(math.floor(fraction * P)), int(seed), int(step),
+                                                ptr_step, _ptr(src), _ptr(rank), _ptr(count), self._stream()), "sg_pbt_select_device")
+        return src
+
+    def pbt_explore_torch(self, src, columns, seed=0, step=0, step_dev=None, refused=None):
+        """PBT's explore step on the device (sg_pbt_explore_device: one launch, graph-capturable).  columns: up to 16 entries
+        (tensor, column, spec): tensor a float32 CUDA tensor [P, C] -- opt.hyper, a population_ppo_grad_torch coef, gae_groups_torch's
+        discounts with one group per member, or any tensor of the caller's; spec = dict(mode=, down=0.8, up=1.25, lo=-inf, hi=inf).
+        For every member m that src lets copy (src[m] != m, in range, and its source not a destination) and every column, the
+        source's value v becomes, by mode: "copy" v; "scale" v f; "scale_complement" 1 - (1 - v) f (gamma, lambda, beta); f is `up`
+        or `down` by one Philox bit of (seed, step, column's position, m); then it is clamped to [lo, hi] and stored in m's row.  Other
+        members keep their bits.  Copies the rule refuses are counted in refused (int32 [1], optional).  Returns refused."""
+        import torch
+        if not (isinstance(src, torch.Tensor) and src.dim() == 1):
+            raise ValueError("src: expected an int32 CUDA tensor [members]")
+        P = self._pbt_members(src.shape[0])
+        self._check_tensor("src", src, torch.int32, (P,))
+        columns = list(columns)
+        if not 1 <= len(columns) <= self.pbt_max_columns:
+            raise ValueError(f"columns: expected 1 .. {self.pbt_max_columns} entries, got {len(columns)}")
+        tab = (_native.SgPbtColumn * len(columns))()
+        for i, (row, entry) in enumerate(zip(tab, columns)):
+            try:
+                t, col, spec = entry
+                spec = dict(spec)
+            except (TypeError, ValueError):
+                raise ValueError(f"columns[{i}]: expected (tensor, column, spec) with spec a dict") from None
+            if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+                raise ValueError(f"columns[{i}]: expected a float32 CUDA tensor [{P}, C]")
+            self._check_tensor(f"columns[{i}] tensor", t, torch.float32, (P, t.shape[1]))
+            if not (isinstance(col, (int, np.integer)) and 0 <= col < t.shape[1]):
+                raise ValueError(f"columns[{i}]: column {col!r} outside the tensor's 0 .. {t.shape[1] - 1}")
+            unknown = set(spec) - {"mode", "down", "up", "lo", "hi"}
+            if unknown or "mode" not in spec:
+                raise ValueError(f"columns[{i}]: spec takes mode (required), down, up, lo, hi" + (f"; got {sorted(unknown)}" if unknown else ""))
+            mode = self.pbt_modes.get(spec["mode"], spec["mode"]) if isinstance(spec["mode"], str) else spec["mode"]
+            if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in self.pbt_modes.values():
+                raise ValueError(f"columns[{i}]: unknown mode {spec['mode']!r}; expected one of {sorted(self.pbt_modes)}")
+            down, up = float(spec.get("down", 0.8)), float(spec.get("up", 1.25))
+            lo, hi = float(spec.get("lo", float("-inf"))), float(spec.get("hi", float("inf")))
+            if any(math.isnan(x) for x in (down, up, lo, hi)):
+                raise ValueError(f"columns[{i}]: down, up, lo and hi must not be NaN")
+            if lo > hi:
+                raise ValueError(f"columns[{i}]: lo = {lo} above hi = {hi}")
+            row.data, row.stride, row.mode = t.data_ptr() + 4 * int(col), int(t.shape[1]), int(mode)
+            row.down, row.up, row.lo, row.hi = down, up, lo, hi
+        ptr_step = self._pbt_step_dev(step_dev)
+        if refused is not None:
+            self._check_tensor("refused", refused, torch.int32, (1,))
+        self._ck(self._lib.sg_pbt_explore_device(self._h, P, _ptr(src), len(tab), tab, int(seed), int(step), ptr_step, _ptr(refused), self._stream()),
+                 "sg_pbt_explore_device")
         return refused
 
     def population_evaluate_torch(self, pop, obs, action):

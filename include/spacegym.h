@@ -1243,6 +1243,41 @@ typedef struct sg_pbt_column {
 int sg_pbt_explore_device(sg_env *env, int32_t members, const int32_t *src, int32_t n_columns, const sg_pbt_column *columns, uint64_t seed,
                           uint64_t step, const int64_t *step_dev, int32_t *refused_out, void *hip_stream);
 
+/* SHUFFLED MINIBATCH INDICES of an on-policy update, drawn on the device: the int64 index that sg_ppo_grad_device and
+ * sg_ppo_population_grad_device gather by, a fresh shuffle of the rollout's rows per epoch cut into minibatches, as a pure function
+ * of (seed, step + step_dev[0], epoch, member, position).  One launch, no sort, no workspace, no atomics; takes the stream,
+ * allocates nothing, never synchronises, hipGraph-capturable; the env's state is not read.  tests/minibatch_model.py states all of
+ * it in NumPy and is the contract; DESIGN section 30 has the kernel.
+ *   B = num_envs, P = members (1 .. 256, dividing B), E = B / P: member m owns the envs [m E, (m + 1) E) (the block rule of the
+ *   population calls).  The rollout is K = steps rows of B envs flattened to rows t B + i, K B < 2^31.  M = minibatches.
+ *   index_out  int64 DEVICE [epochs, M, P, n]: every [e, b] is a contiguous [P, n] block, sg_ppo_population_grad_device's index
+ *              (with P = 1, sg_ppo_grad_device's [n]).
+ * KEYS.  step' = step + step_dev[0] (a 64-bit wrapping sum; step_dev int64 DEVICE [1], may be NULL), so a captured graph draws
+ * afresh when the caller bumps it inside the graph.  For member m and epoch e (0 .. 63), two Philox4x32-10 blocks, key = seed,
+ * counter = ((e << 16) | (blk << 8) | m, step' lo, step' hi, 11) for blk = 0, 1 -- stream tag 11, after explore's 10 -- give the
+ * round keys k[4 blk + i] = o_i.
+ * ONE ENCRYPTION of x in [0, 2^bits), bits = max(2, bit_length(N - 1)), wa = bits / 2, wb = bits - wa: L = x >> wb,
+ * R = x & (2^wb - 1), (a, b) = (wa, wb); for r = 0 .. 7: t = fmix32(R + k[r] mod 2^32) >> (32 - a), (L, R) = (R, L ^ t),
+ * (a, b) = (b, a); the result is (L << b) | R.  fmix32 is murmur3's finaliser (x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13,
+ * x *= 0xC2B2AE35, x ^= x >> 16).  An 8-round unbalanced Feistel network: a bijection of [0, 2^bits).
+ * pi(j) encrypts j and encrypts again while the value is >= N (cycle walking): a bijection of [0, N); 2^bits < 2 N for N >= 3, so
+ * fewer than 2 encryptions are expected.  (The kernel stops a walk after 64 encryptions, which no element is expected to reach.)
+ * NOT CLAIMED: uniformity over all N! orders -- at tiny N the network is visibly non-uniform over them.  Single positions and pairs
+ * are uniform at the sizes anyone trains with; tests/test_minibatch.py states the conditions.
+ *   SG_MINIBATCH_ROW  N = K E, n = N / M (integer division); index[e, b, m, i] = (j / E) B + m E + (j mod E), j = pi_{m,e}(b n + i).
+ *                     The N - M n < M rows left over are another set in every epoch.
+ *   SG_MINIBATCH_ENV  whole env columns stay together: N = E, c = E / M, n = K c; index[e, b, m, t c + i] = t B + m E + pi_{m,e}(b c + i):
+ *                     a time-major [K, c] view.
+ * Within one (e, m) all M n entries are distinct and lie in member m's env block.
+ * sg_minibatch_size returns n, or -1 and a message for a shape that sg_minibatch_index_device refuses.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): steps < 1; members outside 1 .. 256 or not dividing num_envs; epochs
+ * outside 1 .. 64; minibatches < 1; n < 1; K B >= 2^31; an unknown unit; a null index_out. */
+#define SG_MINIBATCH_ROW 0
+#define SG_MINIBATCH_ENV 1
+int64_t sg_minibatch_size(sg_env *env, int32_t steps, int32_t members, int32_t minibatches, int32_t unit);
+int sg_minibatch_index_device(sg_env *env, int32_t steps, int32_t members, int32_t epochs, int32_t minibatches, int32_t unit, uint64_t seed,
+                              uint64_t step, const int64_t *step_dev, int64_t *index_out, void *hip_stream);
+
 /* The off-policy learner's nets (TD3 / DDPG): one or two Q critics on (obs, action) rows, their parameter gradients and d Q / d action,
  * and the actor's action as a differentiable function of its parameters, so that a critic's d Q / d a reaches the actor on the device.
  * Continuous ids only (a 2-vector action); a discrete id is refused with a message.  The reference has no counterpart.

@@ -334,6 +334,8 @@ SYMBOLS = {
     "sg_pbt_fitness_clear_device": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp]),
     "sg_pbt_select_device": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "sg_pbt_explore_device": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, C.POINTER(SgPbtColumn), C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    "sg_minibatch_size": (C.c_int64, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sg_minibatch_index_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "sg_get_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_set_state": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sg_vector_field": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -325,7 +325,8 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "dqn_evaluate_torch", "dqn_evaluate_raw_torch", "dqn_grad_torch", "policy_population_torch", "population_member_torch",
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
                "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
-               "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch")
+               "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch", "minibatch_index_torch",
+               "ppo_update_torch")
 
 
 class SpaceGymVectorEnv:
@@ -2211,6 +2212,105 @@ class SpaceGymVectorEnv:
         self._ck(self._lib.sg_pbt_explore_device(self._h, P, _ptr(src), len(tab), tab, int(seed), int(step), ptr_step, _ptr(refused), self._stream()),
                  "sg_pbt_explore_device")
         return refused
+
+    # ------------------------------------------------------------------ shuffled minibatch indices drawn on the device; the whole PPO update in one call
+    minibatch_units = {"row": 0, "env": 1}  # SG_MINIBATCH_ROW / SG_MINIBATCH_ENV
+    minibatch_max_members, minibatch_max_epochs = 256, 64
+
+    def _minibatch_shape(self, steps, members, epochs, minibatches, unit):
+        """checks the arguments of minibatch_index_torch and returns (K, P, epochs, M, unit's number, n)"""
+        ints = {}
+        for name, v in (("steps", steps), ("members", 1 if members is None else members), ("epochs", epochs), ("minibatches", minibatches)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name}: expected an integer, got {v!r}")
+            ints[name] = int(v)
+        K, P, epochs, M = ints["steps"], ints["members"], ints["epochs"], ints["minibatches"]
+        if K < 1:
+            raise ValueError(f"steps must be at least 1, got {K}")
+        if not 1 <= P <= self.minibatch_max_members:
+            raise ValueError(f"members must be 1 .. {self.minibatch_max_members}, got {P}")
+        if self.num_envs % P:
+            raise ValueError(f"members: {P} does not divide num_envs = {self.num_envs} (member m owns the envs [m B / P, (m + 1) B / P))")
+        if not 1 <= epochs <= self.minibatch_max_epochs:
+            raise ValueError(f"epochs must be 1 .. {self.minibatch_max_epochs}, got {epochs}")
+        if M < 1:
+            raise ValueError(f"minibatches must be at least 1, got {M}")
+        u = self.minibatch_units.get(unit) if isinstance(unit, str) else unit
+        if isinstance(u, bool) or not isinstance(u, (int, np.integer)) or int(u) not in self.minibatch_units.values():
+            raise ValueError(f"unit: unknown unit {unit!r}; expected one of {sorted(self.minibatch_units)}")
+        if K * self.num_envs >= 2 ** 31:
+            raise ValueError(f"steps: {K} steps of {self.num_envs} envs are 2^31 rows or more")
+        E = self.num_envs // P
+        n = (K * E) // M if int(u) == 0 else K * (E // M)
+        if n < 1:
+            raise ValueError(f"minibatches: {M} minibatches of a member's {K * E if int(u) == 0 else E} {'rows' if int(u) == 0 else 'envs'} "
+                             "leave none for a minibatch")
+        return K, P, epochs, M, int(u), n
+
+    def minibatch_index_torch(self, steps, members=None, epochs=1, minibatches=1, unit="row", seed=0, step=0, step_dev=None, out=None):
+        """Shuffled minibatch indices of an on-policy update, drawn on the device (sg_minibatch_index_device: one launch, no sort, no
+        workspace, no host synchronisation, graph-capturable): int64 [epochs, M, P, n] over the rows t B + i of a flattened rollout of
+        `steps` = K rows; every index[e, b] is the [P, n] index of population_ppo_grad_torch, inside member m's env block
+        [m B / P, (m + 1) B / P) for row m.  members None: one policy, the result is [epochs, M, n] and index[e, b] is ppo_grad_torch's
+        [n].  unit "row": a member's K B / P rows are shuffled afresh per epoch and cut into M minibatches of n = (K B / P) // M (the
+        fewer than M rows left over are another set in every epoch); unit "env": its B / P env columns are shuffled and a minibatch holds
+        c = (B / P) // M whole columns, n = K c, index[e, b, m] a time-major [K, c] view.  Within one (epoch, member) no row repeats.
+        An index is a pure function of (seed, step + step_dev, epoch, member, position) -- a keyed bijection, tests/minibatch_model.py;
+        uniform in single positions and pairs, not over all orders.  step_dev: int64 CUDA tensor [1] added to step on the device -- bump
+        it inside a captured graph and every replay shuffles afresh.  out: the tensor to fill.  Returns the index."""
+        import torch
+        K, P, epochs, M, u, n = self._minibatch_shape(steps, members, epochs, minibatches, unit)
+        shape = (epochs, M, n) if members is None else (epochs, M, P, n)
+        ptr_step = self._pbt_step_dev(step_dev)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=torch.device("cuda", self.device))
+        else:
+            self._check_tensor("out", out, torch.int64, shape)
+        self._ck(self._lib.sg_minibatch_index_device(self._h, K, P, epochs, M, u, int(seed), int(step), ptr_step, _ptr(out), self._stream()),
+                 "sg_minibatch_index_device")
+        return out
+
+    def ppo_update_torch(self, handle, opt, batch, steps, epochs, minibatches, unit="row", seed=0, step=0, step_dev=None, coef=None,
+                         clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, index=None, stats=None,
+                         grads=None):
+        """The whole PPO update of one rollout in one call: epochs x minibatches times (shuffled index, gradient, Adam step).  A
+        COMPOSITION OF EXISTING ENTRY POINTS THAT ADDS NO NATIVE CODE: one minibatch_index_torch call, then for every (e, b)
+        ppo_grad_torch (handle a policy_torch handle) or population_ppo_grad_torch (a policy_population_torch handle, with coef) with
+        index[e, b], out=grads and stats=stats[e, b], followed by adam_step_torch(opt, grads).  No host synchronisation; graph-capturable
+        after one warm-up call, as the calls it makes are.  batch: ppo_grad_torch's dict over the steps * num_envs rows of the flattened
+        rollout; opt: adam_torch's state of `handle`; steps, epochs, minibatches, unit, seed, step, step_dev: minibatch_index_torch's;
+        the loss keywords: ppo_grad_torch's.  index / stats / grads: the tensors to fill (int64 [epochs, M, (P,) n]; float32
+        [epochs, M, (P,) 12]; a gradient dict), made when None.  Returns (stats, index)."""
+        import torch
+        pop = isinstance(handle, PolicyPopulation)
+        if not pop:
+            self._net_handle(handle, Policy)
+            if coef is not None:
+                raise ValueError("coef: per-member coefficients belong to a population; pass the four scalars")
+        P = self._population(handle, per_env=True) if pop else None
+        if coef is not None:
+            self._check_tensor("coef", coef, torch.float32, (P, len(self.ppo_coef_names)))
+        if not isinstance(opt, AdamState) or opt.handle is not handle:
+            raise ValueError("opt: expected the AdamState adam_torch returned for this handle")
+        K, _, epochs, M, _, n = self._minibatch_shape(steps, P, epochs, minibatches, unit)
+        obs, R, _ = self._ppo_batch(handle, batch, clip_range, clip_range_vf, ent_coef, vf_coef, coef=coef is not None)
+        if R != K * self.num_envs:
+            raise ValueError(f"batch: {R} rows, but steps * num_envs = {K * self.num_envs}")
+        lead = (epochs, M, P) if pop else (epochs, M)
+        if stats is None:
+            stats = obs.new_empty((*lead, len(self.ppo_stats_names)))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (*lead, len(self.ppo_stats_names)))
+        index = self.minibatch_index_torch(K, P, epochs, M, unit, seed, step, step_dev, out=index)
+        loss = dict(clip_range=clip_range, clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage)
+        for e in range(epochs):
+            for b in range(M):
+                if pop:
+                    grads, _ = self.population_ppo_grad_torch(handle, batch, index[e, b], coef=coef, out=grads, stats=stats[e, b], **loss)
+                else:
+                    grads, _ = self.ppo_grad_torch(handle, batch, index[e, b], out=grads, stats=stats[e, b], **loss)
+                self.adam_step_torch(opt, grads)
+        return stats, index
 
     def population_evaluate_torch(self, pop, obs, action):
         """logp, entropy, value, each [P, n], of the stored rows under the CURRENT parameters, differentiable with respect to the

@@ -1499,6 +1499,69 @@ int sg_dqn_grad_device(sg_env *env, const sg_dqn *dqn, int64_t n, const float *o
 /* Bytes of workspace sg_dqn_grad_device needs for n rows (it grows with n up to a cap); 0 and an error message for an invalid dqn or n */
 size_t sg_dqn_grad_workspace_bytes(sg_env *env, const sg_dqn *dqn, int64_t n);
 
+/* THE DQN / DOUBLE DQN TD UPDATE IN ONE CALL: from a replay batch (sg_replay_sample_device's columns), an online and a target sg_dqn of
+ * one architecture to the TD target, the Huber loss, its statistics and the ONLINE net's parameter gradients -- the two
+ * sg_dqn_evaluate_device calls on next_obs, the target arithmetic, the loss and sg_dqn_grad_device of a hand-composed update, without
+ * autograd.  For row i, with Q the six head outputs, argmax and Q[a] exactly sg_dqn_evaluate_device's:
+ *     a*      = argmax Q_online(next_obs[i])                                   (double_q; the first maximum)
+ *     q_next  = Q_target(next_obs[i])[a*]                                      (double_q == 0: max_j Q_target(next_obs[i])[j])
+ *     y       = terminated[i] ? reward[i] : reward[i] + discount[i] * q_next   the product rounded, then the sum: never an fma
+ *     q_taken = Q_online(obs[i])[action[i]];  td = q_taken - y
+ *     c       = min(max(td, -huber_delta), +huber_delta);  w = weight ? weight[i] : 1
+ *     g       = (w * c) / (float)n                                             the product rounded, then the quotient
+ *     loss    = (1 / n) sum_i w * (|td| <= huber_delta ? 0.5 td^2 : huber_delta (|td| - 0.5 huber_delta))
+ * and g goes to sg_dqn_grad_device's backward as g_taken.  discount is the batch's per-row column (gamma^steps as the n-step sampler
+ * writes it): there is no separate gamma.  A terminated row never multiplies its q_next (an infinite one leaves y = reward).
+ * huber_delta = +inf gives the squared loss 0.5 td^2.  Everything is float32.  Every other loss on the Q values goes through
+ * sg_dqn_evaluate_device / sg_dqn_grad_device. */
+typedef struct sg_dqn_td_config {
+    uint32_t struct_size; /* sizeof(sg_dqn_td_config) */
+    int32_t double_q;     /* default 1; 0: plain DQN, the target net's maximum */
+    float huber_delta;    /* > 0; +inf: the squared loss.  Default 1 */
+    int32_t reserved;     /* 0 */
+} sg_dqn_td_config;
+void sg_dqn_td_config_init(sg_dqn_td_config *cfg);
+/* Device pointers to the n rows of the batch */
+typedef struct sg_dqn_td_batch {
+    const float *obs;          /* float32 [n, obs_dim] */
+    const int32_t *action;     /* int32 [n], 0 .. 5 */
+    const float *reward;       /* float32 [n] (the n-step return's reward part) */
+    const float *next_obs;     /* float32 [n, obs_dim] */
+    const uint8_t *terminated; /* uint8 [n] */
+    const float *discount;     /* float32 [n] */
+    const float *weight;       /* float32 [n] importance weights on the loss; may be NULL (ones) */
+} sg_dqn_td_batch;
+/* Optional per-row outputs, float32 [n], each may be NULL: the numbers the kernels used for row i */
+typedef struct sg_dqn_td_rows {
+    float *td_error; /* q_taken - y, signed: what sg_priority_update_device's caller raises to alpha */
+    float *q_taken;
+    float *target;   /* y */
+    float *q_next;
+    float *g;
+} sg_dqn_td_rows;
+/* grads (an sg_dqn_grads with every slot of the net given) receives d loss / d theta of the ONLINE net, WRITTEN, not accumulated: bit
+ * for bit what sg_dqn_grad_device gives at the same n for (obs, action) with g_taken = row_out->g.  row_out->q_next / q_taken are
+ * sg_dqn_evaluate_device's bits for the same rows.
+ * stats_out float32 [8]: loss, td_abs_mean = mean |td|, td_abs_max = max |td| (exactly the largest |row_out->td_error|), q_mean = mean
+ * q_taken, target_mean = mean y, clip_fraction = mean(|td| > huber_delta), weight_mean, bad_rows.
+ * An action outside 0 .. 5 is never an index (every selection compares); such a row contributes zero to every gradient and statistic,
+ * reports g = 0 and td_error = 0, is counted in bad_rows, and the means still divide by n.
+ * Launches: the target (sg_dqn_evaluate_device's kernel frame; with double_q the online net, then the target net in the same LDS),
+ * which leaves y in `workspace`; the backward -- sg_dqn_grad_device's kernel frame with the loss gradient formed from the head outputs,
+ * every workgroup leaving its statistics sums beside its partial sums; the reduction in workgroup order.  `workspace`: at least
+ * sg_dqn_td_grad_workspace_bytes(env, online, n) bytes of device memory, any content.  Allocates nothing, never synchronises,
+ * hipGraph-capturable.  No atomics: the same inputs and the same n give the same bits.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): whatever sg_dqn_act_device refuses of either dqn (a continuous id
+ * among it); nets that differ in n_hidden, hidden or activation; a null cfg, a wrong struct_size or reserved; a huber_delta that is
+ * NaN or not > 0; n outside 1 .. 2^31 - 1; a null batch, obs, action, reward, next_obs, terminated or discount; a null stats_out; what
+ * sg_dqn_grad_device refuses of grads; a null workspace or one smaller than the query's answer. */
+int sg_dqn_td_grad_device(sg_env *env, const sg_dqn *online, const sg_dqn *target, const sg_dqn_td_config *cfg, const sg_dqn_td_batch *batch,
+                          int64_t n, const sg_dqn_grads *grads, float *stats_out, const sg_dqn_td_rows *row_out, void *workspace,
+                          size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_dqn_td_grad_device needs for n rows: sg_dqn_grad_workspace_bytes', the statistics partials and y float32 [n];
+ * 0 and an error message for an invalid dqn or n */
+size_t sg_dqn_td_grad_workspace_bytes(sg_env *env, const sg_dqn *online, int64_t n);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

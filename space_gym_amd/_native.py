@@ -198,6 +198,22 @@ class SgDqnGrads(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("net", SgPolicyMlp)]
 
 
+class SgDqnTdConfig(C.Structure):
+    """sg_dqn_td_config (include/spacegym.h): sg_dqn_td_config_init fills in double_q 1 and huber_delta 1"""
+    _fields_ = [("struct_size", C.c_uint32), ("double_q", C.c_int32), ("huber_delta", C.c_float), ("reserved", C.c_int32)]
+
+
+class SgDqnTdBatch(C.Structure):
+    """sg_dqn_td_batch (include/spacegym.h): the columns of a replay batch and the optional importance weights"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("next_obs", C.c_void_p), ("terminated", C.c_void_p),
+                ("discount", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class SgDqnTdRows(C.Structure):
+    """sg_dqn_td_rows (include/spacegym.h): optional per-row outputs of sg_dqn_td_grad_device"""
+    _fields_ = [("td_error", C.c_void_p), ("q_taken", C.c_void_p), ("target", C.c_void_p), ("q_next", C.c_void_p), ("g", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -317,6 +333,10 @@ SYMBOLS = {
     "sg_dqn_evaluate_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sg_dqn_grad_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.c_int64, _vp, _vp, _vp, _vp, C.POINTER(SgDqnGrads), _vp, C.c_size_t, _vp]),
     "sg_dqn_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgDqn), C.c_int64]),
+    "sg_dqn_td_config_init": (None, [C.POINTER(SgDqnTdConfig)]),
+    "sg_dqn_td_grad_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.POINTER(SgDqn), C.POINTER(SgDqnTdConfig), C.POINTER(SgDqnTdBatch), C.c_int64,
+                                        C.POINTER(SgDqnGrads), _vp, C.POINTER(SgDqnTdRows), _vp, C.c_size_t, _vp]),
+    "sg_dqn_td_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgDqn), C.c_int64]),
     "sg_policy_population_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
     "sg_rollout_policy_population_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp,
                                                       _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),

@@ -326,7 +326,7 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
                "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
                "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch", "minibatch_index_torch",
-               "ppo_update_torch")
+               "ppo_update_torch", "dqn_td_grad_torch", "dqn_update_torch")
 
 
 class SpaceGymVectorEnv:
@@ -2695,6 +2695,126 @@ class SpaceGymVectorEnv:
             huber(env.dqn_evaluate_torch(online, obs, action)[1], target).mean().backward()"""
         self._dqn_rows(dqn, "dqn_evaluate_torch", obs, action)
         return _net_function("DqnEvaluate", _dqn_forward, _dqn_backward).apply(self, dqn, obs, action, *dqn.tensors)
+
+    # ------------------------------------------------------------------ the Double-DQN TD update: target, Huber loss, statistics and gradients
+    dqn_td_stats_names = ("loss", "td_abs_mean", "td_abs_max", "q_mean", "target_mean", "clip_fraction", "weight_mean", "bad_rows")
+    _DQN_TD_ROWS = ("td_error", "q_taken", "target", "q_next", "g")
+
+    def _dqn_td_batch(self, batch, weight):
+        """checks the replay batch dict of dqn_td_grad_torch and the optional weights; returns (obs, n)"""
+        import torch
+        if not isinstance(batch, dict):
+            raise ValueError("batch: expected the dict replay_sample_torch returns (obs, action, reward, next_obs, terminated, discount)")
+        obs = batch.get("obs")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"batch['obs']: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        spec = (("obs", torch.float32, (n, self.obs_dim)), ("action", torch.int32, (n,)), ("reward", torch.float32, (n,)),
+                ("next_obs", torch.float32, (n, self.obs_dim)), ("terminated", torch.uint8, (n,)), ("discount", torch.float32, (n,)))
+        for k, dtype, shape in spec:
+            if batch.get(k) is None:
+                raise ValueError(f"batch['{k}']: missing")
+            self._check_tensor(f"batch['{k}']", batch[k], dtype, shape)
+        if weight is not None:
+            self._check_tensor("weight", weight, torch.float32, (n,))
+        return obs, n
+
+    def dqn_td_grad_torch(self, online, target, batch, double_q=True, huber_delta=1.0, weight=None, rows=None, out=None, stats=None):
+        """One DQN / Double DQN TD update without autograd (sg_dqn_td_grad_device: the target, the Huber loss, its statistics and the
+        online net's gradients in three launches on torch's current stream; no host synchronisation; graph-capturable after one
+        warm-up call with the same n, which sizes the workspace kept on the online handle).  online, target: dqn_torch handles of one
+        architecture.  batch: the dict replay_sample_torch / replay_sample_prioritized_torch return -- obs [n, D], action int32 [n],
+        reward, next_obs [n, D], terminated uint8, discount (the per-row n-step discount: there is no separate gamma).  double_q: the
+        online net's argmax on next_obs evaluated by the target net (False: the target net's maximum).  huber_delta: > 0;
+        float("inf") gives 0.5 td^2.  weight: float32 [n] importance weights on the loss (a prioritized batch's weight).  Returns
+        (grads, stats): grads is dqn_grad_torch's dict (net: the list of (weight, bias) gradients), WRITTEN, not accumulated (out:
+        such a dict to fill), accepted by adam_step_torch as is; stats float32 [8], named by dqn_td_stats_names (stats: the tensor
+        to fill).  rows: optional dict td_error (q_taken - target, signed) / q_taken / target / q_next / g of float32 [n] tensors
+        that receive the per-row numbers the kernels used.  A row whose action is outside 0 .. 5 adds nothing and is counted in
+        bad_rows.  Same inputs and same n: the same bits.  include/spacegym.h states the arithmetic."""
+        import math
+        import torch
+        self._dqn_handle(online, "dqn_td_grad_torch")
+        self._net_handle(target, Dqn)
+        if (online.n_hidden, online.hidden, online.activation) != (target.n_hidden, target.hidden, target.activation):
+            raise ValueError("target: expected a net of the online net's architecture (n_hidden, hidden, activation): "
+                             f"{(target.n_hidden, target.hidden, target.activation)} against {(online.n_hidden, online.hidden, online.activation)}")
+        obs, n = self._dqn_td_batch(batch, weight)
+        try:
+            delta = float(huber_delta)
+        except (TypeError, ValueError):
+            raise ValueError(f"huber_delta: expected a value > 0 (float('inf'): the squared loss), got {huber_delta!r}") from None
+        if math.isnan(delta) or not delta > 0.0:
+            raise ValueError(f"huber_delta: expected a value > 0 (float('inf'): the squared loss), got {huber_delta!r}")
+        r = _native.SgDqnTdRows()
+        if rows is not None:
+            for k, t in rows.items():
+                if k not in self._DQN_TD_ROWS:
+                    raise ValueError(f"rows['{k}']: expected the keys {', '.join(self._DQN_TD_ROWS)}")
+                if t is None:
+                    continue
+                self._check_tensor(f"rows['{k}']", t, torch.float32, (n,))
+                setattr(r, k, t.data_ptr())
+        if out is None:
+            out = dict(net=_empty_pairs(online.tensors))
+        g = _native.SgDqnGrads(struct_size=C.sizeof(_native.SgDqnGrads))
+        self._grad_pairs("out['net']", out["net"], online.tensors, g.net)
+        if stats is None:
+            stats = obs.new_empty(len(self.dqn_td_stats_names))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (len(self.dqn_td_stats_names),))
+        cfg = _native.SgDqnTdConfig()
+        self._lib.sg_dqn_td_config_init(C.byref(cfg))
+        cfg.double_q, cfg.huber_delta = int(bool(double_q)), delta
+        b = _native.SgDqnTdBatch(obs=obs.data_ptr(), action=batch["action"].data_ptr(), reward=batch["reward"].data_ptr(),
+                                 next_obs=batch["next_obs"].data_ptr(), terminated=batch["terminated"].data_ptr(),
+                                 discount=batch["discount"].data_ptr(), weight=weight.data_ptr() if weight is not None else None)
+        ws = self._grad_workspace(online, "sg_dqn_td_grad_workspace_bytes", n, obs.device, "dqn_td_grad_torch", "sg_dqn_td_grad_workspace_bytes")
+        self._ck(self._lib.sg_dqn_td_grad_device(self._h, C.byref(online.struct), C.byref(target.struct), C.byref(cfg), C.byref(b), n, C.byref(g),
+                                                 _ptr(stats), C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()),
+                 "sg_dqn_td_grad_device")
+        return out, stats
+
+    def dqn_update_torch(self, online, target, opt, batch, double_q=True, huber_delta=1.0, weight=None, rows=None, grads=None, stats=None,
+                         prio=None, alpha=0.6, priority_epsilon=1e-6, tau=None):
+        """One whole DQN learner step in one call.  A COMPOSITION OF EXISTING ENTRY POINTS THAT ADDS NO NATIVE CODE:
+        dqn_td_grad_torch(online, target, batch, ...) with out=grads, then adam_step_torch(opt, grads); with prio (a
+        replay_priority_torch handle; batch needs the prioritized sampler's cell) replay_update_priorities_torch(prio, batch['cell'],
+        rows['td_error'], alpha, priority_epsilon); with tau the target's tensors move towards the online ones by
+        torch._foreach_lerp_(target, online, tau) (Polyak averaging).  tau: a float in [0, 1], or a float32 CUDA scalar tensor read
+        on the device, so that a captured graph does a hard sync every N replays by writing 0 or 1 into it.  opt: adam_torch's state
+        of `online`.  No host synchronisation; graph-capturable after one warm-up call, as the calls it makes are (rows and grads
+        are then the caller's tensors, or those of the warm-up call's return).  Returns (stats, rows, grads)."""
+        import torch
+        if not isinstance(opt, AdamState) or opt.handle is not online:
+            raise ValueError("opt: expected the AdamState adam_torch returned for the online handle")
+        if tau is not None:
+            if isinstance(tau, torch.Tensor):
+                self._check_tensor("tau", tau, torch.float32, ())
+            else:
+                try:
+                    tau = float(tau)
+                except (TypeError, ValueError):
+                    raise ValueError(f"tau: expected None, a float in [0, 1] or a float32 CUDA scalar tensor, got {tau!r}") from None
+                if not 0.0 <= tau <= 1.0:
+                    raise ValueError(f"tau: expected None, a float in [0, 1] or a float32 CUDA scalar tensor, got {tau!r}")
+        rows = dict(rows) if rows is not None else {}
+        if prio is not None:
+            if not isinstance(batch, dict) or batch.get("cell") is None:
+                raise ValueError("batch['cell']: missing (prio is given: the batch must be replay_sample_prioritized_torch's)")
+            self._priority_arg(prio)
+            if rows.get("td_error") is None:
+                self._dqn_td_batch(batch, weight)
+                rows["td_error"] = torch.empty_like(batch["reward"])
+        grads, stats = self.dqn_td_grad_torch(online, target, batch, double_q=double_q, huber_delta=huber_delta, weight=weight,
+                                              rows=rows or None, out=grads, stats=stats)
+        self.adam_step_torch(opt, grads)
+        if prio is not None:
+            self.replay_update_priorities_torch(prio, batch["cell"], rows["td_error"], alpha=alpha, epsilon=priority_epsilon)
+        if tau is not None:
+            with torch.no_grad():  # (the target's tensors may be nn.Parameters)
+                torch._foreach_lerp_(list(target.tensors), list(online.tensors), [tau] * len(target.tensors) if isinstance(tau, torch.Tensor) else tau)
+        return stats, rows, grads
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

@@ -95,16 +95,25 @@ def case(obs_dim, n, hidden, n_hidden, seed):
     float32, with the tight BOUNDS.  Any observation row whose float64 raw_d lies within MARGIN of a bound is redrawn (deterministically,
     from the case's own generator) until none does: a float32 / float64 disagreement about the clamp mask would move a summed gradient
     by O(1).  No row is left out."""
+    return case_of(obs_dim, n, hidden, n_hidden, seed)
+
+
+def case_of(obs_dim, n, hidden, n_hidden, seed, bounds=BOUNDS, prepare=None):
+    """case() under other clamp bounds and with the freshly drawn actor passed through `prepare` (tests/net_regimes.py scales it) before
+    the redraw rule is applied to it: the same draws in the same order"""
     rng = np.random.default_rng([seed, obs_dim, n, hidden, n_hidden])
     actor = random_squashed(rng, obs_dim, hidden, n_hidden)
+    if prepare is not None:
+        actor = prepare(actor)
     obs = rng.standard_normal((n, obs_dim)).astype(np.float32)
     eps = rng.standard_normal((n, 2)).astype(np.float32)
     ga = rng.standard_normal((n, 2)).astype(np.float32)
     gl = rng.standard_normal(n).astype(np.float32)
+    lo, hi = float(np.float32(bounds[0])), float(np.float32(bounds[1]))
     for activation in ("tanh", "relu"):  # the same rows serve both activations
         for _ in range(100):
             raw = _forward(actor, obs, activation, np.float64)[2][:, 2:]
-            near = (np.minimum(np.abs(raw - BOUNDS[0]), np.abs(raw - BOUNDS[1])) < MARGIN).any(axis=1)
+            near = (np.minimum(np.abs(raw - lo), np.abs(raw - hi)) < MARGIN).any(axis=1)
             if not near.any():
                 break
             obs[near] = rng.standard_normal((int(near.sum()), obs_dim)).astype(np.float32)
@@ -112,7 +121,7 @@ def case(obs_dim, n, hidden, n_hidden, seed):
             raise AssertionError("case: rows near a clamp bound remain")
     for activation in ("tanh", "relu"):
         raw = _forward(actor, obs, activation, np.float64)[2][:, 2:]
-        assert not (np.minimum(np.abs(raw - BOUNDS[0]), np.abs(raw - BOUNDS[1])) < MARGIN).any()
+        assert not (np.minimum(np.abs(raw - lo), np.abs(raw - hi)) < MARGIN).any()
     return dict(actor=actor, obs=obs, eps=eps, g_action=ga, g_logp=gl)
 
 
@@ -136,8 +145,8 @@ def grad_cases():
 SELECTIONS = ("both", "action", "logp")
 
 
-def grad_reference(c, activation, selection, dtype):
+def grad_reference(c, activation, selection, dtype, bounds=BOUNDS):
     """flat gradients of a case under a selection of the loss gradients"""
     ga = c["g_action"] if selection in ("both", "action") else None
     gl = c["g_logp"] if selection in ("both", "logp") else None
-    return flat(sample(c["actor"], c["obs"], c["eps"], ga, gl, bounds=BOUNDS, activation=activation, dtype=dtype))
+    return flat(sample(c["actor"], c["obs"], c["eps"], ga, gl, bounds=bounds, activation=activation, dtype=dtype))

@@ -1562,6 +1562,91 @@ int sg_dqn_td_grad_device(sg_env *env, const sg_dqn *online, const sg_dqn *targe
  * 0 and an error message for an invalid dqn or n */
 size_t sg_dqn_td_grad_workspace_bytes(sg_env *env, const sg_dqn *online, int64_t n);
 
+/* THE TD CRITIC UPDATE OF SAC, TD3 AND DDPG IN ONE CALL: from a replay batch (sg_replay_sample_device's columns), the target action the
+ * caller formed, an online and a target sg_qnet of one shape to the TD target, the Huber loss, its statistics and the ONLINE critics'
+ * parameter gradients -- the target critics' sg_q_evaluate_device, the minimum, SAC's entropy term or TD3's target smoothing, the loss and
+ * sg_q_grad_device of a hand-composed update, without autograd.  THE TARGET ACTION IS AN INPUT: next_action (and SAC's next_logp) come
+ * from one launch of the caller's actor on next_obs (sg_squashed_act_device, or sg_policy_action_device on the target actor), so the
+ * call fixes no actor's form.  For row i, with Qc the critic c of sg_q_evaluate_device on [obs | action], bit for bit:
+ *     a'_d    = next_action[i][d]
+ *               noise given:  e = min(max(noise_std * noise[i][d], -noise_clip), noise_clip)
+ *                             a'_d = min(max(a'_d + e, -action_clip), action_clip)            (noise NULL: a' used as given, never clamped)
+ *     q_next  = min(Q1_target(next_obs[i], a'), Q2_target(next_obs[i], a'))                   (one critic: Q1_target)
+ *               next_logp given:  q_next = q_next - alpha * next_logp[i]                      (alpha = *alpha_dev when given, else cfg.alpha)
+ *     y       = terminated[i] ? reward[i] : reward[i] + discount[i] * q_next                  a select; every product rounded, never an fma
+ *     per critic c of the ONLINE qnet:  q_c = Qc(obs[i], action[i]);  td_c = q_c - y
+ *               cl_c = min(max(td_c, -huber_delta), huber_delta);  w = weight ? weight[i] : 1;  g_c = (w * cl_c) / (float)n
+ *               l_c  = w * (|td_c| <= huber_delta ? 0.5 td_c^2 : huber_delta (|td_c| - 0.5 huber_delta))
+ *     loss    = (1 / n) sum_i (l_1 + l_2)
+ * and g_c goes to sg_q_grad_device's backward as g_qc.  discount is the batch's per-row column (gamma^steps as the n-step sampler writes
+ * it): there is no separate gamma.  A terminated row never multiplies its q_next (an infinite one leaves y = reward).  huber_delta =
+ * +inf, the default, gives 0.5 td^2 per critic: HALF of the sum of the two mean squared errors that CleanRL's and SB3's TD3 / SAC
+ * minimise (their gradients are twice these); there is no scale parameter -- fold the factor into the learning rate.  Every min, max
+ * and clamp hands a NaN on, as torch.minimum and torch.clamp do: non-finite inputs propagate as they do in torch, and no row is set
+ * aside.  Everything is float32.  The actor's and alpha's steps are not part of this: they stay sg_squashed_grad_device /
+ * sg_q_grad_device calls.  tests/q_td_model.py states all of it in NumPy; DESIGN section 32 has the kernels and the tolerances. */
+typedef struct sg_q_td_config {
+    uint32_t struct_size; /* sizeof(sg_q_td_config) */
+    float huber_delta;    /* > 0; +inf: the squared loss.  Default +inf */
+    float alpha;          /* the entropy coefficient when batch.alpha_dev is NULL; read only with batch.next_logp.  Default 0.2 */
+    float noise_std;      /* >= 0; read only with batch.noise.  Default 0.2 */
+    float noise_clip;     /* >= 0, +inf: none.  Default 0.5 */
+    float action_clip;    /* >= 0, +inf: none; a' is clamped only when batch.noise is given.  Default 1 */
+    int32_t reserved[2];  /* 0 */
+} sg_q_td_config;
+void sg_q_td_config_init(sg_q_td_config *cfg);
+/* Device pointers to the n rows of the batch */
+typedef struct sg_q_td_batch {
+    const float *obs;          /* float32 [n, obs_dim] */
+    const float *action;       /* float32 [n, 2] */
+    const float *reward;       /* float32 [n] (the n-step return's reward part) */
+    const float *next_obs;     /* float32 [n, obs_dim] */
+    const uint8_t *terminated; /* uint8 [n] */
+    const float *discount;     /* float32 [n] */
+    const float *next_action;  /* float32 [n, 2]: the actor's action at next_obs */
+    const float *weight;       /* float32 [n] importance weights on the loss; may be NULL (ones) */
+    const float *next_logp;    /* float32 [n] log-prob of next_action (SAC); may be NULL: no entropy term */
+    const float *alpha_dev;    /* one float32 on the device, read by the kernel, so that a learned alpha changes inside a captured graph;
+                                  may be NULL (cfg.alpha); needs next_logp */
+    const float *noise;        /* float32 [n, 2] standard normal draws (TD3's target smoothing); may be NULL: a' = next_action */
+} sg_q_td_batch;
+/* Optional per-row outputs, float32 [n], each may be NULL: the numbers the kernels used for row i */
+typedef struct sg_q_td_rows {
+    float *td1;    /* q_1 - y, signed */
+    float *td2;
+    float *q1;
+    float *q2;
+    float *target; /* y */
+    float *q_next; /* after the entropy term */
+    float *g1;
+    float *g2;
+    float *td_abs; /* 0.5 (|td1| + |td2|); one critic: |td1|.  What sg_priority_update_device's caller raises to alpha */
+} sg_q_td_rows;
+/* grads (an sg_qnet_grads with every slot of every critic in use given) receives d loss / d theta of the ONLINE critics, WRITTEN, not
+ * accumulated: bit for bit what sg_q_grad_device gives at the same n for (obs, action) with g_q1 = row_out->g1, g_q2 = row_out->g2.
+ * row_out->q1 / q2 are sg_q_evaluate_device's bits of the online qnet for the same rows; row_out->q_next before the entropy term is
+ * the minimum of the target qnet's at (next_obs, a').
+ * stats_out float32 [9]: loss, td1_abs_mean = mean |td1|, td2_abs_mean, td_abs_max = max over both critics (exactly the largest of
+ * |row_out->td1| and |row_out->td2|), q1_mean, q2_mean, target_mean = mean y, clip_fraction = #(|td_c| > huber_delta) / (critics * n),
+ * weight_mean.  With one critic the critic-2 entries are 0.
+ * Launches: the target (sg_q_evaluate_device's kernel frame on the target qnet, a' in registers, critic 0 and then critic 1 in the same
+ * LDS), which leaves y in `workspace`; the backward -- sg_q_grad_device's kernel frame with no action gradient and the loss gradient
+ * formed from the head output, every workgroup leaving its statistics sums beside its partial sums; the reduction in workgroup order.
+ * `workspace`: at least sg_q_td_grad_workspace_bytes(env, online, n) bytes of device memory aligned to 4, any content.  Allocates
+ * nothing, never synchronises, hipGraph-capturable.  Every sum has a fixed order that is a function of n: the same inputs and the same
+ * n give the same bits.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a discrete id; whatever sg_q_evaluate_device refuses of either qnet; qnets
+ * that differ in n_critics, n_hidden, hidden or activation; a null cfg, a wrong struct_size or reserved; a huber_delta that is NaN or
+ * not > 0; a negative or NaN noise_std, noise_clip or action_clip; n outside 1 .. 2^31 - 1; a null batch, obs, action, reward, next_obs,
+ * terminated, discount or next_action; alpha_dev without next_logp; td2, q2 or g2 of row_out with one critic; a null stats_out; what
+ * sg_q_grad_device refuses of grads (grads is mandatory here); a null, short or misaligned workspace. */
+int sg_q_td_grad_device(sg_env *env, const sg_qnet *online, const sg_qnet *target, const sg_q_td_config *cfg, const sg_q_td_batch *batch,
+                        int64_t n, const sg_qnet_grads *grads, float *stats_out, const sg_q_td_rows *row_out, void *workspace,
+                        size_t workspace_bytes, void *hip_stream);
+/* Bytes of workspace sg_q_td_grad_device needs for n rows: sg_q_grad_workspace_bytes', 36 bytes of statistics partials per workgroup and
+ * y float32 [n]; 0 and an error message for an invalid qnet or n */
+size_t sg_q_td_grad_workspace_bytes(sg_env *env, const sg_qnet *online, int64_t n);
+
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its
  * current ship state (ship == NULL) or the given one (float32 [num_envs, 6]).  Host arrays; actions as in sg_step. */

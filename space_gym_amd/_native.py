@@ -214,6 +214,27 @@ class SgDqnTdRows(C.Structure):
     _fields_ = [("td_error", C.c_void_p), ("q_taken", C.c_void_p), ("target", C.c_void_p), ("q_next", C.c_void_p), ("g", C.c_void_p)]
 
 
+class SgQTdConfig(C.Structure):
+    """sg_q_td_config (include/spacegym.h): sg_q_td_config_init fills in huber_delta +inf, alpha 0.2, noise_std 0.2, noise_clip 0.5 and
+    action_clip 1"""
+    _fields_ = [("struct_size", C.c_uint32), ("huber_delta", C.c_float), ("alpha", C.c_float), ("noise_std", C.c_float),
+                ("noise_clip", C.c_float), ("action_clip", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class SgQTdBatch(C.Structure):
+    """sg_q_td_batch (include/spacegym.h): the columns of a replay batch, the target action and the optional weights, log-probs, device
+    alpha and smoothing noise"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("next_obs", C.c_void_p), ("terminated", C.c_void_p),
+                ("discount", C.c_void_p), ("next_action", C.c_void_p), ("weight", C.c_void_p), ("next_logp", C.c_void_p),
+                ("alpha_dev", C.c_void_p), ("noise", C.c_void_p)]
+
+
+class SgQTdRows(C.Structure):
+    """sg_q_td_rows (include/spacegym.h): optional per-row outputs of sg_q_td_grad_device"""
+    _fields_ = [("td1", C.c_void_p), ("td2", C.c_void_p), ("q1", C.c_void_p), ("q2", C.c_void_p), ("target", C.c_void_p),
+                ("q_next", C.c_void_p), ("g1", C.c_void_p), ("g2", C.c_void_p), ("td_abs", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -337,6 +358,10 @@ SYMBOLS = {
     "sg_dqn_td_grad_device": (C.c_int, [_vp, C.POINTER(SgDqn), C.POINTER(SgDqn), C.POINTER(SgDqnTdConfig), C.POINTER(SgDqnTdBatch), C.c_int64,
                                         C.POINTER(SgDqnGrads), _vp, C.POINTER(SgDqnTdRows), _vp, C.c_size_t, _vp]),
     "sg_dqn_td_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgDqn), C.c_int64]),
+    "sg_q_td_config_init": (None, [C.POINTER(SgQTdConfig)]),
+    "sg_q_td_grad_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.POINTER(SgQnet), C.POINTER(SgQTdConfig), C.POINTER(SgQTdBatch), C.c_int64,
+                                      C.POINTER(SgQnetGrads), _vp, C.POINTER(SgQTdRows), _vp, C.c_size_t, _vp]),
+    "sg_q_td_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgQnet), C.c_int64]),
     "sg_policy_population_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
     "sg_rollout_policy_population_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp,
                                                       _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),

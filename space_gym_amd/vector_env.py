@@ -326,7 +326,8 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "population_act_torch", "rollout_population_torch", "population_evaluate_torch", "population_evaluate_raw_torch",
                "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
                "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch", "minibatch_index_torch",
-               "ppo_update_torch", "dqn_td_grad_torch", "dqn_update_torch")
+               "ppo_update_torch", "dqn_td_grad_torch", "dqn_update_torch", "q_td_grad_torch",
+               "q_update_torch")
 
 
 class SpaceGymVectorEnv:
@@ -2785,6 +2786,14 @@ class SpaceGymVectorEnv:
         on the device, so that a captured graph does a hard sync every N replays by writing 0 or 1 into it.  opt: adam_torch's state
         of `online`.  No host synchronisation; graph-capturable after one warm-up call, as the calls it makes are (rows and grads
         are then the caller's tensors, or those of the warm-up call's return).  Returns (stats, rows, grads)."""
+        return self._td_update(online, target, opt, batch, rows, "td_error", lambda: self._dqn_td_batch(batch, weight),
+                               lambda rows: self.dqn_td_grad_torch(online, target, batch, double_q=double_q, huber_delta=huber_delta, weight=weight,
+                                                                   rows=rows, out=grads, stats=stats),
+                               prio, alpha, priority_epsilon, tau)
+
+    def _td_update(self, online, target, opt, batch, rows, priority_row, check_batch, grad_call, prio, priority_alpha, priority_epsilon, tau):
+        """what dqn_update_torch and q_update_torch share: the checks of opt, tau and a prioritized batch, grad_call(rows) -> (grads,
+        stats) with rows[priority_row] made when prio needs it (after check_batch()), the Adam step, the priority update and the lerp"""
         import torch
         if not isinstance(opt, AdamState) or opt.handle is not online:
             raise ValueError("opt: expected the AdamState adam_torch returned for the online handle")
@@ -2803,18 +2812,156 @@ class SpaceGymVectorEnv:
             if not isinstance(batch, dict) or batch.get("cell") is None:
                 raise ValueError("batch['cell']: missing (prio is given: the batch must be replay_sample_prioritized_torch's)")
             self._priority_arg(prio)
-            if rows.get("td_error") is None:
-                self._dqn_td_batch(batch, weight)
-                rows["td_error"] = torch.empty_like(batch["reward"])
-        grads, stats = self.dqn_td_grad_torch(online, target, batch, double_q=double_q, huber_delta=huber_delta, weight=weight,
-                                              rows=rows or None, out=grads, stats=stats)
+            if rows.get(priority_row) is None:
+                check_batch()
+                rows[priority_row] = torch.empty_like(batch["reward"])
+        grads, stats = grad_call(rows or None)
         self.adam_step_torch(opt, grads)
         if prio is not None:
-            self.replay_update_priorities_torch(prio, batch["cell"], rows["td_error"], alpha=alpha, epsilon=priority_epsilon)
+            self.replay_update_priorities_torch(prio, batch["cell"], rows[priority_row], alpha=priority_alpha, epsilon=priority_epsilon)
         if tau is not None:
             with torch.no_grad():  # (the target's tensors may be nn.Parameters)
                 torch._foreach_lerp_(list(target.tensors), list(online.tensors), [tau] * len(target.tensors) if isinstance(tau, torch.Tensor) else tau)
         return stats, rows, grads
+
+    # ------------------------------------------------------------------ the TD critic update of SAC / TD3 / DDPG: target, Huber loss, statistics and gradients
+    q_td_stats_names = ("loss", "td1_abs_mean", "td2_abs_mean", "td_abs_max", "q1_mean", "q2_mean", "target_mean", "clip_fraction", "weight_mean")
+    _Q_TD_ROWS = ("td1", "td2", "q1", "q2", "target", "q_next", "g1", "g2", "td_abs")
+
+    def _q_td_batch(self, batch, next_action, next_logp, noise, weight):
+        """checks the replay batch dict of q_td_grad_torch and the columns beside it; returns (obs, n)"""
+        import torch
+        if not isinstance(batch, dict):
+            raise ValueError("batch: expected the dict replay_sample_torch returns (obs, action, reward, next_obs, terminated, discount)")
+        obs = batch.get("obs")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or int(obs.shape[0]) < 1:
+            raise ValueError(f"batch['obs']: expected a CUDA tensor of shape (n, {self.obs_dim}) with n >= 1")
+        n = int(obs.shape[0])
+        spec = (("obs", torch.float32, (n, self.obs_dim)), ("action", torch.float32, (n, 2)), ("reward", torch.float32, (n,)),
+                ("next_obs", torch.float32, (n, self.obs_dim)), ("terminated", torch.uint8, (n,)), ("discount", torch.float32, (n,)))
+        for k, dtype, shape in spec:
+            if batch.get(k) is None:
+                raise ValueError(f"batch['{k}']: missing")
+            self._check_tensor(f"batch['{k}']", batch[k], dtype, shape)
+        if next_action is None:
+            raise ValueError("next_action: expected the actor's float32 [n, 2] action at batch['next_obs']")
+        self._check_tensor("next_action", next_action, torch.float32, (n, 2))
+        for name, t, shape in (("next_logp", next_logp, (n,)), ("noise", noise, (n, 2)), ("weight", weight, (n,))):
+            if t is not None:
+                self._check_tensor(name, t, torch.float32, shape)
+        return obs, n
+
+    def q_td_grad_torch(self, online, target, batch, next_action, next_logp=None, alpha=0.2, noise=None, noise_std=0.2, noise_clip=0.5,
+                        action_clip=1.0, huber_delta=float("inf"), weight=None, rows=None, out=None, stats=None):
+        """One TD critic update of SAC, TD3 or DDPG without autograd (sg_q_td_grad_device: the target, the Huber loss, its statistics
+        and the online critics' gradients in three launches on torch's current stream; no host synchronisation; graph-capturable
+        after one warm-up call with the same n, which sizes the workspace kept on the online handle).  online, target: q_torch
+        handles of one shape.  batch: the dict replay_sample_torch / replay_sample_prioritized_torch return -- obs [n, D], action
+        [n, 2], reward, next_obs [n, D], terminated uint8, discount (the per-row n-step discount: there is no separate gamma).
+        next_action float32 [n, 2]: the actor's action at next_obs, from one launch of the caller's --
+          SAC   next_action, next_logp = squashed_act_torch(sp, batch['next_obs'], seed, step); alpha: a float, or a one-element
+                float32 CUDA tensor read on the device (a learned alpha changes inside a captured graph): q_next -= alpha * next_logp
+          TD3   next_action = policy_action_raw_torch(target_actor, batch['next_obs']); noise float32 [n, 2] standard normal draws:
+                a' = clamp(next_action + clamp(noise_std * noise, -noise_clip, noise_clip), -action_clip, action_clip)
+          DDPG  next_action alone, one critic: used as given, never clamped.
+        huber_delta: > 0; the default float("inf") gives 0.5 td^2 PER CRITIC, half of the sum of the two mean squared errors that
+        CleanRL's and SB3's TD3 / SAC minimise: their gradients are twice these (fold the factor into the learning rate).  weight:
+        float32 [n] importance weights on the loss (a prioritized batch's weight).  Returns (grads, stats): grads is q_grad_torch's
+        dict (critics: per critic the list of (weight, bias) gradients; action None), WRITTEN, not accumulated (out: such a dict to
+        fill), accepted by adam_step_torch as is; stats float32 [9], named by q_td_stats_names (stats: the tensor to fill; with one
+        critic the critic-2 entries are 0).  rows: optional dict td1 / td2 / q1 / q2 / target / q_next / g1 / g2 / td_abs of float32
+        [n] tensors that receive the per-row numbers the kernels used; td_abs = 0.5 (|td1| + |td2|) (one critic: |td1|) is what
+        replay_update_priorities_torch takes.  Same inputs and same n: the same bits.  include/spacegym.h states the arithmetic."""
+        import math
+        import torch
+        self._net_handle(online, QNet, "q_td_grad_torch")
+        self._net_handle(target, QNet)
+        shape = lambda q: (q.n_critics, q.n_hidden, q.hidden, q.activation)
+        if shape(online) != shape(target):
+            raise ValueError("target: expected critics of the online handle's shape (n_critics, n_hidden, hidden, activation): "
+                             f"{shape(target)} against {shape(online)}")
+        obs, n = self._q_td_batch(batch, next_action, next_logp, noise, weight)
+
+        def number(name, v, ok, what):
+            try:
+                x = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name}: expected {what}, got {v!r}") from None
+            if math.isnan(x) or not ok(x):
+                raise ValueError(f"{name}: expected {what}, got {v!r}")
+            return x
+        delta = number("huber_delta", huber_delta, lambda x: x > 0.0, "a value > 0 (float('inf'): the squared loss)")
+        noise_std = number("noise_std", noise_std, lambda x: x >= 0.0, "a value >= 0")
+        noise_clip = number("noise_clip", noise_clip, lambda x: x >= 0.0, "a value >= 0 (float('inf'): no clamp)")
+        action_clip = number("action_clip", action_clip, lambda x: x >= 0.0, "a value >= 0 (float('inf'): no clamp)")
+        alpha_dev = None
+        if isinstance(alpha, torch.Tensor):
+            if next_logp is None:
+                raise ValueError("alpha: a tensor is read only with next_logp (it scales the entropy term)")
+            self._check_tensor("alpha", alpha, torch.float32, tuple(alpha.shape))
+            if alpha.numel() != 1:
+                raise ValueError(f"alpha: expected a float or a one-element float32 CUDA tensor, got shape {tuple(alpha.shape)}")
+            alpha_dev, alpha = alpha, 0.0
+        else:
+            alpha = number("alpha", alpha, lambda x: True, "a float or a one-element float32 CUDA tensor")
+        r = _native.SgQTdRows()
+        if rows is not None:
+            for k, t in rows.items():
+                if k not in self._Q_TD_ROWS:
+                    raise ValueError(f"rows['{k}']: expected the keys {', '.join(self._Q_TD_ROWS)}")
+                if t is None:
+                    continue
+                if k in ("td2", "q2", "g2") and online.n_critics != 2:
+                    raise ValueError(f"rows['{k}']: the handle has one critic")
+                self._check_tensor(f"rows['{k}']", t, torch.float32, (n,))
+                setattr(r, k, t.data_ptr())
+        L = online.n_hidden + 1
+        like = [online.tensors[2 * L * c:2 * L * (c + 1)] for c in range(online.n_critics)]
+        if out is None:
+            out = dict(critics=[_empty_pairs(ts) for ts in like], action=None)
+        elif out.get("critics") is None:
+            raise ValueError("out['critics']: the critics' gradients need tensors")
+        g = _native.SgQnetGrads(struct_size=C.sizeof(_native.SgQnetGrads))
+        nets = [list(c) for c in out["critics"]]
+        if len(nets) != online.n_critics:
+            raise ValueError(f"out['critics']: expected {online.n_critics} nets, got {len(nets)}")
+        for c, pairs in enumerate(nets):
+            self._grad_pairs(f"out['critics'][{c}]", pairs, like[c], g.critic[c])
+        if stats is None:
+            stats = obs.new_empty(len(self.q_td_stats_names))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (len(self.q_td_stats_names),))
+        cfg = _native.SgQTdConfig()
+        self._lib.sg_q_td_config_init(C.byref(cfg))
+        cfg.huber_delta, cfg.alpha, cfg.noise_std, cfg.noise_clip, cfg.action_clip = delta, alpha, noise_std, noise_clip, action_clip
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        b = _native.SgQTdBatch(obs=obs.data_ptr(), action=batch["action"].data_ptr(), reward=batch["reward"].data_ptr(),
+                               next_obs=batch["next_obs"].data_ptr(), terminated=batch["terminated"].data_ptr(),
+                               discount=batch["discount"].data_ptr(), next_action=next_action.data_ptr(), weight=ptr(weight),
+                               next_logp=ptr(next_logp), alpha_dev=ptr(alpha_dev), noise=ptr(noise))
+        ws = self._grad_workspace(online, "sg_q_td_grad_workspace_bytes", n, obs.device, "q_td_grad_torch", "sg_q_td_grad_workspace_bytes")
+        self._ck(self._lib.sg_q_td_grad_device(self._h, C.byref(online.struct), C.byref(target.struct), C.byref(cfg), C.byref(b), n, C.byref(g),
+                                               _ptr(stats), C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()),
+                 "sg_q_td_grad_device")
+        return out, stats
+
+    def q_update_torch(self, online, target, opt, batch, next_action, next_logp=None, alpha=0.2, noise=None, noise_std=0.2, noise_clip=0.5,
+                       action_clip=1.0, huber_delta=float("inf"), weight=None, rows=None, grads=None, stats=None, prio=None,
+                       priority_alpha=0.6, priority_epsilon=1e-6, tau=None):
+        """One whole critic step of SAC / TD3 / DDPG in one call.  A COMPOSITION OF EXISTING ENTRY POINTS THAT ADDS NO NATIVE CODE:
+        q_td_grad_torch(online, target, batch, next_action, ...) with out=grads, then adam_step_torch(opt, grads); with prio (a
+        replay_priority_torch handle; batch needs the prioritized sampler's cell) replay_update_priorities_torch(prio, batch['cell'],
+        rows['td_abs'], priority_alpha, priority_epsilon); with tau the target's tensors move towards the online ones by
+        torch._foreach_lerp_(target, online, tau) (Polyak averaging).  tau: a float in [0, 1], or a float32 CUDA scalar tensor read
+        on the device.  opt: adam_torch's state of `online`.  The actor's and alpha's steps stay the caller's (squashed_grad_torch /
+        q_grad_torch: the losses differ per learner).  No host synchronisation; graph-capturable after one warm-up call, as the calls
+        it makes are (rows and grads are then the caller's tensors, or those of the warm-up call's return).  Returns (stats, rows,
+        grads)."""
+        return self._td_update(online, target, opt, batch, rows, "td_abs", lambda: self._q_td_batch(batch, next_action, next_logp, noise, weight),
+                               lambda rows: self.q_td_grad_torch(online, target, batch, next_action, next_logp=next_logp, alpha=alpha, noise=noise,
+                                                                 noise_std=noise_std, noise_clip=noise_clip, action_clip=action_clip,
+                                                                 huber_delta=huber_delta, weight=weight, rows=rows, out=grads, stats=stats),
+                               prio, priority_alpha, priority_epsilon, tau)
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

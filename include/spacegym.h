@@ -1583,8 +1583,9 @@ size_t sg_dqn_td_grad_workspace_bytes(sg_env *env, const sg_dqn *online, int64_t
  * +inf, the default, gives 0.5 td^2 per critic: HALF of the sum of the two mean squared errors that CleanRL's and SB3's TD3 / SAC
  * minimise (their gradients are twice these); there is no scale parameter -- fold the factor into the learning rate.  Every min, max
  * and clamp hands a NaN on, as torch.minimum and torch.clamp do: non-finite inputs propagate as they do in torch, and no row is set
- * aside.  Everything is float32.  The actor's and alpha's steps are not part of this: they stay sg_squashed_grad_device /
- * sg_q_grad_device calls.  tests/q_td_model.py states all of it in NumPy; DESIGN section 32 has the kernels and the tolerances. */
+ * aside.  Everything is float32.  The actor's and alpha's steps are not part of this: the actor's is sg_q_actor_squashed_grad_device /
+ * sg_q_actor_gaussian_grad_device.  tests/q_td_model.py states all of it in NumPy; DESIGN section 32 has the kernels and the
+ * tolerances. */
 typedef struct sg_q_td_config {
     uint32_t struct_size; /* sizeof(sg_q_td_config) */
     float huber_delta;    /* > 0; +inf: the squared loss.  Default +inf */
@@ -1646,6 +1647,72 @@ int sg_q_td_grad_device(sg_env *env, const sg_qnet *online, const sg_qnet *targe
 /* Bytes of workspace sg_q_td_grad_device needs for n rows: sg_q_grad_workspace_bytes', 36 bytes of statistics partials per workgroup and
  * y float32 [n]; 0 and an error message for an invalid qnet or n */
 size_t sg_q_td_grad_workspace_bytes(sg_env *env, const sg_qnet *online, int64_t n);
+
+/* THE ACTOR UPDATE OF SAC, TD3 AND DDPG THROUGH THE TWIN Q CRITICS IN ONE CALL: from observations, the actor and an sg_qnet to the
+ * action, the critics' values and action gradients, the loss mean(alpha logp - Q), its statistics and the ACTOR's parameter gradients --
+ * sg_squashed_sample_device, sg_q_evaluate_device, the selection of the smaller critic, sg_q_grad_device for d Q / d action and
+ * sg_squashed_grad_device (or sg_policy_action_device / sg_policy_action_grad_device) of a hand-composed step, without autograd and with
+ * the critics run once.  Two entry points, one per actor struct, share everything else.  For row i, bit for bit:
+ *     head     = actor MLP(obs[i])
+ *     squashed: (a, logp) = sg_squashed_sample_device's of (head, eps[i])              (eps NULL: zeros)
+ *     gaussian: a_d = fmaf(expf(log_std_d), eps[i][d], head_d), sg_policy_action_device's;  logp = 0 and alpha must be 0
+ *     critic c: q_c = Qc(obs[i], a), sg_q_evaluate_device's;  dq_c[d] = 0.0f + d Qc / d a_d, sg_q_grad_device's g_action_out for g_qc = 1
+ *     q_select = 1: both critics run, sel2 = q2 < q1 || q2 != q2 (ties to critic 1; a NaN q2 is taken, as torch.minimum hands it on)
+ *     q_select = 0: critic 1 alone, sel2 = false
+ *     q_sel = sel2 ? q2 : q1;  loss_i = alpha * logp - q_sel                     two roundings, never an fma; alpha = *alpha_dev when given
+ *     g_action[d] = (-dq_sel[d]) / (float)n;  g_logp = alpha / (float)n
+ * and (g_action, g_logp) go to sg_squashed_grad_device's backward (g_action to sg_policy_action_grad_device's).  The critics' parameters
+ * get no gradient.  Everything is float32.  tests/q_actor_model.py states all of it in NumPy; DESIGN section 33 has the kernels. */
+typedef struct sg_q_actor_config {
+    uint32_t struct_size; /* sizeof(sg_q_actor_config) */
+    float alpha;          /* >= 0: the entropy coefficient when alpha_dev is NULL; 0 for the Gaussian form.  Default 0.2 */
+    float target_entropy; /* stats_out[8] = -(logp_mean + target_entropy).  Default -2 (minus the action dimensions) */
+    int32_t q_select;     /* 1: the minimum of two critics; 0: critic 1; -1, the default: 1 for the squashed actor on two critics, else 0 */
+    int32_t reserved[2];  /* 0 */
+} sg_q_actor_config;
+void sg_q_actor_config_init(sg_q_actor_config *cfg);
+/* Optional per-row outputs, each may be NULL: the numbers the kernel used for row i */
+typedef struct sg_q_actor_rows {
+    float *action;   /* float32 [n, 2] */
+    float *logp;     /* float32 [n] (the Gaussian form: 0) */
+    float *q1;       /* float32 [n] */
+    float *q2;       /* float32 [n]; q_select = 1 only */
+    float *q_sel;    /* float32 [n] */
+    float *dq1_da;   /* float32 [n, 2] */
+    float *dq2_da;   /* float32 [n, 2]; q_select = 1 only */
+    float *g_action; /* float32 [n, 2] */
+} sg_q_actor_rows;
+/* grads receives d loss / d theta of the actor (the Gaussian form: and of log_std), WRITTEN, not accumulated: bit for bit what
+ * sg_squashed_grad_device gives for (obs, eps, g_action = row_out->g_action, g_logp = alpha / n) wherever the row tile of the larger of
+ * the two nets' width classes (hidden up to 32 / 64 / 96 / 128: 256 / 128 / 64 / 64 rows) is the actor's own class's; with another tile
+ * the same sums are grouped differently.  alpha_dev: one float32 on the device, read by the kernel, so that a learned temperature
+ * changes inside a captured graph; may be NULL (cfg.alpha).
+ * stats_out float32 [9]: loss, logp_mean, q1_mean, q2_mean (0 when critic 2 did not run), q_sel_mean, critic2_fraction = #sel2 / n,
+ * action_abs_mean = mean 0.5 (|a_0| + |a_1|), dq_da_abs_max over the critics run and both components (a NaN entry makes it NaN, as it
+ * makes the sums), log_alpha_grad = -(logp_mean + target_entropy): the gradient of SB3's temperature loss by log_alpha (the Gaussian
+ * form: 0).  eps and the [n, 2] row outputs are read and written as pairs: aligned to 8 bytes, as a tensor's rows are.
+ * Launches: the gradient kernel (sg_q_grad_device's kernel frame with both nets; per row tile the actor's forward, each critic's
+ * forward and walk to the action, the actor's backward) and the reduction in workgroup order.  `workspace`: at least
+ * sg_q_actor_grad_workspace_bytes(...) bytes of device memory aligned to 4, any content.  Allocates nothing, never synchronises,
+ * hipGraph-capturable.  Every sum has a fixed order that is a function of n: the same inputs and the same n give the same bits.
+ * Refused (SG_ERR_INVALID, with a message, nothing enqueued): a discrete id; whatever sg_squashed_sample_device / sg_policy_action_device
+ * refuses of the actor and sg_q_evaluate_device of the qnet; a null cfg, a wrong struct_size or reserved; q_select outside -1 .. 1, or 1
+ * with one critic; alpha NaN or negative; a non-zero alpha or an alpha_dev with the Gaussian form; a NaN target_entropy; n outside
+ * 1 .. 2^31 - 1; a null obs, stats_out or grads; q2 or dq2_da of row_out when critic 2 does not run; what sg_squashed_grad_device /
+ * sg_policy_action_grad_device refuse of grads; a null, short or misaligned workspace. */
+int sg_q_actor_squashed_grad_device(sg_env *env, const sg_squashed_policy *actor, const sg_qnet *qnet, const sg_q_actor_config *cfg,
+                                    int64_t n, const float *obs, const float *eps, const float *alpha_dev,
+                                    const sg_squashed_grads *grads, float *stats_out, const sg_q_actor_rows *row_out, void *workspace,
+                                    size_t workspace_bytes, void *hip_stream);
+int sg_q_actor_gaussian_grad_device(sg_env *env, const sg_policy *actor, const sg_qnet *qnet, const sg_q_actor_config *cfg, int64_t n,
+                                    const float *obs, const float *eps, const float *alpha_dev, const sg_policy_grads *grads,
+                                    float *stats_out, const sg_q_actor_rows *row_out, void *workspace, size_t workspace_bytes,
+                                    void *hip_stream);
+/* Bytes of workspace either call needs for n rows, exactly one of the two actors given: per workgroup (of the larger class's tile, at
+ * most 256) the actor's partial sums as its own grad call lays them out and 32 bytes of statistics partials; 0 and an error message for
+ * an invalid actor, qnet or n */
+size_t sg_q_actor_grad_workspace_bytes(sg_env *env, const sg_squashed_policy *squashed, const sg_policy *gaussian, const sg_qnet *qnet,
+                                       int64_t n);
 
 /* SpaceshipEnv.vector_field(raw_action, state_vec=None) (spaceship_env.py:96-100): the RHS of the ODE,
  * out float32 [num_envs, 6] = (vx, vy, omega', ax, ay, angular acceleration) at each env's current planets and either its

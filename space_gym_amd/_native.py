@@ -235,6 +235,19 @@ class SgQTdRows(C.Structure):
                 ("q_next", C.c_void_p), ("g1", C.c_void_p), ("g2", C.c_void_p), ("td_abs", C.c_void_p)]
 
 
+class SgQActorConfig(C.Structure):
+    """sg_q_actor_config (include/spacegym.h): sg_q_actor_config_init fills in alpha 0.2, target_entropy -2 and q_select -1 (the default:
+    the minimum for the squashed actor on two critics, else critic 1)"""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha", C.c_float), ("target_entropy", C.c_float), ("q_select", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class SgQActorRows(C.Structure):
+    """sg_q_actor_rows (include/spacegym.h): optional per-row outputs of sg_q_actor_squashed_grad_device / sg_q_actor_gaussian_grad_device"""
+    _fields_ = [("action", C.c_void_p), ("logp", C.c_void_p), ("q1", C.c_void_p), ("q2", C.c_void_p), ("q_sel", C.c_void_p),
+                ("dq1_da", C.c_void_p), ("dq2_da", C.c_void_p), ("g_action", C.c_void_p)]
+
+
 class SgCounters(C.Structure):
     _fields_ = [("env_steps", C.c_uint64), ("episodes_finished", C.c_uint64), ("truncations", C.c_uint64), ("goal_hits", C.c_uint64)]
 
@@ -362,6 +375,12 @@ SYMBOLS = {
     "sg_q_td_grad_device": (C.c_int, [_vp, C.POINTER(SgQnet), C.POINTER(SgQnet), C.POINTER(SgQTdConfig), C.POINTER(SgQTdBatch), C.c_int64,
                                       C.POINTER(SgQnetGrads), _vp, C.POINTER(SgQTdRows), _vp, C.c_size_t, _vp]),
     "sg_q_td_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgQnet), C.c_int64]),
+    "sg_q_actor_config_init": (None, [C.POINTER(SgQActorConfig)]),
+    "sg_q_actor_squashed_grad_device": (C.c_int, [_vp, C.POINTER(SgSquashedPolicy), C.POINTER(SgQnet), C.POINTER(SgQActorConfig), C.c_int64, _vp, _vp,
+                                                  _vp, C.POINTER(SgSquashedGrads), _vp, C.POINTER(SgQActorRows), _vp, C.c_size_t, _vp]),
+    "sg_q_actor_gaussian_grad_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.POINTER(SgQnet), C.POINTER(SgQActorConfig), C.c_int64, _vp, _vp, _vp,
+                                                  C.POINTER(SgPolicyGrads), _vp, C.POINTER(SgQActorRows), _vp, C.c_size_t, _vp]),
+    "sg_q_actor_grad_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(SgSquashedPolicy), C.POINTER(SgPolicy), C.POINTER(SgQnet), C.c_int64]),
     "sg_policy_population_act_device": (C.c_int, [_vp, C.POINTER(SgPolicy), C.c_int32, _vp, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp]),
     "sg_rollout_policy_population_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgPolicy), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _vp, _vp,
                                                       _vp, _vp, _vp, _vp, _vp, C.POINTER(SgTerminalList), _vp, _vp]),

@@ -327,7 +327,7 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
                "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch", "minibatch_index_torch",
                "ppo_update_torch", "dqn_td_grad_torch", "dqn_update_torch", "q_td_grad_torch",
-               "q_update_torch")
+               "q_update_torch", "q_actor_grad_torch", "q_actor_update_torch")
 
 
 class SpaceGymVectorEnv:
@@ -1433,12 +1433,14 @@ class SpaceGymVectorEnv:
             self._check_tensor(f"{name}[{l}] bias", b, torch.float32, tuple(like[2 * l + 1].shape))
             mlp.weight[l], mlp.bias[l] = w.data_ptr(), b.data_ptr()
 
-    def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None, members=None):
+    def _grad_workspace(self, handle, bytes_fn, n, device, who, refused=None, members=None, query=None):
         """the workspace tensor cached on a Policy / QNet / SquashedPolicy / Dqn / PolicyPopulation handle, grown when n needs more -- never
         inside a capture; refused: what the error names when the engine refuses the net or n (default: who); members: a population's,
-        which its query takes before n"""
+        which its query takes before n; query: the arguments of bytes_fn after the env, where they are not (the handle's struct, n)"""
         import torch
-        need = int(getattr(self._lib, bytes_fn)(self._h, C.byref(handle.struct), *((n,) if members is None else (members, n))))
+        if query is None:
+            query = (C.byref(handle.struct), *((n,) if members is None else (members, n)))
+        need = int(getattr(self._lib, bytes_fn)(self._h, *query))
         if need == 0:
             self._ck(-1, refused or who)
         ws = handle.workspace
@@ -2953,8 +2955,8 @@ class SpaceGymVectorEnv:
         replay_priority_torch handle; batch needs the prioritized sampler's cell) replay_update_priorities_torch(prio, batch['cell'],
         rows['td_abs'], priority_alpha, priority_epsilon); with tau the target's tensors move towards the online ones by
         torch._foreach_lerp_(target, online, tau) (Polyak averaging).  tau: a float in [0, 1], or a float32 CUDA scalar tensor read
-        on the device.  opt: adam_torch's state of `online`.  The actor's and alpha's steps stay the caller's (squashed_grad_torch /
-        q_grad_torch: the losses differ per learner).  No host synchronisation; graph-capturable after one warm-up call, as the calls
+        on the device.  opt: adam_torch's state of `online`.  The actor's step is q_actor_update_torch; alpha's stays
+        the caller's.  No host synchronisation; graph-capturable after one warm-up call, as the calls
         it makes are (rows and grads are then the caller's tensors, or those of the warm-up call's return).  Returns (stats, rows,
         grads)."""
         return self._td_update(online, target, opt, batch, rows, "td_abs", lambda: self._q_td_batch(batch, next_action, next_logp, noise, weight),
@@ -2962,6 +2964,124 @@ class SpaceGymVectorEnv:
                                                                  noise_std=noise_std, noise_clip=noise_clip, action_clip=action_clip,
                                                                  huber_delta=huber_delta, weight=weight, rows=rows, out=grads, stats=stats),
                                prio, priority_alpha, priority_epsilon, tau)
+
+    # ------------------------------------------------------------------ the actor update of SAC / TD3 / DDPG through the twin Q critics
+    q_actor_stats_names = ("loss", "logp_mean", "q1_mean", "q2_mean", "q_sel_mean", "critic2_fraction", "action_abs_mean", "dq_da_abs_max",
+                           "log_alpha_grad")
+    _Q_ACTOR_ROWS = dict(action=2, logp=1, q1=1, q2=1, q_sel=1, dq1_da=2, dq2_da=2, g_action=2)  # the columns of each row output
+
+    def q_actor_grad_torch(self, actor, q, obs, eps=None, alpha=0.2, q_select=None, target_entropy=-2.0, rows=None, out=None, stats=None):
+        """One actor update of SAC, TD3 or DDPG without autograd (sg_q_actor_squashed_grad_device / sg_q_actor_gaussian_grad_device: the
+        action, the critics' values and action gradients, the loss mean(alpha logp - Q), its statistics and the actor's gradients in two
+        launches on torch's current stream, the critics run once; no host synchronisation; graph-capturable after one warm-up call
+        with the same n, which sizes the workspace kept on the actor handle).  actor: a squashed_policy_torch handle (SAC; with
+        eps=None, alpha=0 a deterministic tanh actor), or a continuous policy_torch handle, whose action is policy_action_raw_torch's
+        mean + exp(log_std) eps (TD3 / DDPG: eps=None, or the exploration noise; alpha must stay 0).  q: a q_torch handle.  obs
+        float32 [n, D]; eps float32 [n, 2] standard normal draws or None (zeros).  alpha: a float >= 0, or a one-element float32 CUDA
+        tensor read on the device (a learned temperature changes inside a captured graph).  q_select: 1 takes the smaller of two
+        critics per row (ties and a NaN as torch.minimum), 0 critic 1 alone; None: 1 for a squashed actor on two critics, else 0.
+        Returns (grads, stats): grads is squashed_grad_torch's dict (actor) or policy_action_grad_torch's (actor, log_std), WRITTEN,
+        not accumulated (out: such a dict to fill), accepted by adam_step_torch as is; the critics get no gradient.  stats float32
+        [9], named by q_actor_stats_names (stats: the tensor to fill): q2_mean and critic2_fraction are 0 when critic 2 did not run;
+        log_alpha_grad = -(logp_mean + target_entropy) is the gradient of SB3's temperature loss by log_alpha (0 for a policy_torch
+        actor), so the temperature step is the caller's three lines:
+            log_alpha -= lr * stats[8]; alpha.copy_(log_alpha.exp())      (alpha: the tensor the calls read)
+        rows: optional dict action [n, 2] / logp / q1 / q2 / q_sel / dq1_da [n, 2] / dq2_da [n, 2] / g_action [n, 2] of float32
+        tensors that receive the per-row numbers the kernel used.  Same inputs and same n: the same bits.  include/spacegym.h states
+        the arithmetic."""
+        import math
+        import torch
+        who = "q_actor_grad_torch"
+        squashed = isinstance(actor, SquashedPolicy)
+        if not squashed and not isinstance(actor, Policy):
+            raise ValueError("actor: expected the handle squashed_policy_torch returns, or the one policy_torch returns for a continuous id")
+        n = self._net_rows(actor, SquashedPolicy if squashed else Policy, obs, who, eps=eps)
+        self._net_handle(q, QNet, who)
+        if q_select is None:
+            q_select = 1 if squashed and q.n_critics == 2 else 0
+        if isinstance(q_select, bool) or q_select not in (0, 1):
+            raise ValueError(f"q_select: expected None, 0 (critic 1) or 1 (the minimum of two critics), got {q_select!r}")
+        if q_select == 1 and q.n_critics != 2:
+            raise ValueError("q_select: 1 takes the minimum of two critics, but the handle has one critic")
+        alpha_dev = None
+        if isinstance(alpha, torch.Tensor):
+            if not squashed:
+                raise ValueError("alpha: the policy_torch actor has no log-prob term: alpha must be 0")
+            self._check_tensor("alpha", alpha, torch.float32, tuple(alpha.shape))
+            if alpha.numel() != 1:
+                raise ValueError(f"alpha: expected a float >= 0 or a one-element float32 CUDA tensor, got shape {tuple(alpha.shape)}")
+            alpha_dev, alpha = alpha, 0.0
+        else:
+            try:
+                alpha = float(alpha)
+            except (TypeError, ValueError):
+                raise ValueError(f"alpha: expected a float >= 0 or a one-element float32 CUDA tensor, got {alpha!r}") from None
+            if math.isnan(alpha) or alpha < 0.0:
+                raise ValueError(f"alpha: expected a float >= 0 or a one-element float32 CUDA tensor, got {alpha!r}")
+            if not squashed and alpha != 0.0:
+                raise ValueError("alpha: the policy_torch actor has no log-prob term: alpha must be 0")
+        try:
+            target_entropy = float(target_entropy)
+        except (TypeError, ValueError):
+            raise ValueError(f"target_entropy: expected a float, got {target_entropy!r}") from None
+        if math.isnan(target_entropy):
+            raise ValueError(f"target_entropy: expected a float, got {target_entropy!r}")
+        r = _native.SgQActorRows()
+        if rows is not None:
+            for k, t in rows.items():
+                if k not in self._Q_ACTOR_ROWS:
+                    raise ValueError(f"rows['{k}']: expected the keys {', '.join(self._Q_ACTOR_ROWS)}")
+                if t is None:
+                    continue
+                if k in ("q2", "dq2_da") and not q_select:
+                    raise ValueError(f"rows['{k}']: critic 2 does not run (q_select is 0)")
+                self._check_tensor(f"rows['{k}']", t, torch.float32, (n, 2) if self._Q_ACTOR_ROWS[k] == 2 else (n,))
+                setattr(r, k, t.data_ptr())
+        if squashed:
+            if out is None:
+                out = dict(actor=_empty_pairs(actor.tensors))
+            g = _native.SgSquashedGrads(struct_size=C.sizeof(_native.SgSquashedGrads))
+            self._grad_pairs("out['actor']", out["actor"], actor.tensors, g.actor)
+        else:
+            a_par = actor.tensors[:2 * (actor.n_hidden + 1)]
+            if out is None:
+                out = dict(actor=_empty_pairs(a_par), log_std=torch.empty_like(actor.tensors[-1]))
+            g = _native.SgPolicyGrads(struct_size=C.sizeof(_native.SgPolicyGrads))
+            self._grad_pairs("out['actor']", out["actor"], a_par, g.actor)
+            if out.get("log_std") is None:
+                raise ValueError("out['log_std']: expected a float32 [2] tensor")
+            self._check_tensor("out['log_std']", out["log_std"], torch.float32, (2,))
+            g.log_std = out["log_std"].data_ptr()
+        if stats is None:
+            stats = obs.new_empty(len(self.q_actor_stats_names))
+        else:
+            self._check_tensor("stats", stats, torch.float32, (len(self.q_actor_stats_names),))
+        cfg = _native.SgQActorConfig()
+        self._lib.sg_q_actor_config_init(C.byref(cfg))
+        cfg.alpha, cfg.target_entropy, cfg.q_select = alpha, target_entropy, q_select
+        a_ref = C.byref(actor.struct)
+        ws = self._grad_workspace(actor, "sg_q_actor_grad_workspace_bytes", n, obs.device, who, "sg_q_actor_grad_workspace_bytes",
+                                  query=(a_ref if squashed else None, None if squashed else a_ref, C.byref(q.struct), n))
+        fn = "sg_q_actor_squashed_grad_device" if squashed else "sg_q_actor_gaussian_grad_device"
+        self._ck(getattr(self._lib, fn)(self._h, a_ref, C.byref(q.struct), C.byref(cfg), n, _ptr(obs), _ptr(eps), _ptr(alpha_dev), C.byref(g),
+                                        _ptr(stats), C.byref(r) if rows is not None else None, _ptr(ws), ws.numel(), self._stream()), fn)
+        return out, stats
+
+    def q_actor_update_torch(self, actor, q, opt, obs, eps=None, alpha=0.2, q_select=None, target_entropy=-2.0, rows=None, grads=None,
+                             stats=None):
+        """One whole actor step of SAC / TD3 / DDPG in one call.  A COMPOSITION OF EXISTING ENTRY POINTS THAT ADDS NO NATIVE CODE:
+        q_actor_grad_torch(actor, q, obs, eps, ...) with out=grads, then adam_step_torch(opt, grads).  opt: adam_torch's state of
+        `actor`.  The temperature's step stays the caller's (q_actor_grad_torch gives its three lines).  With q_update_torch before it
+        this is the whole update of the continuous off-policy learners on the device.  No host synchronisation; graph-capturable
+        after one warm-up call, as the calls it makes are (rows and grads are then the caller's tensors, or those of the warm-up
+        call's return).  Returns (stats, rows, grads)."""
+        if not isinstance(opt, AdamState) or opt.handle is not actor:
+            raise ValueError("opt: expected the AdamState adam_torch returned for the actor handle")
+        rows = dict(rows) if rows is not None else {}
+        grads, stats = self.q_actor_grad_torch(actor, q, obs, eps=eps, alpha=alpha, q_select=q_select, target_entropy=target_entropy,
+                                               rows=rows or None, out=grads, stats=stats)
+        self.adam_step_torch(opt, grads)
+        return stats, rows, grads
 
     def gae(self, reward, done, trunc, value=None, last_value=None, terminal_value=None, terminal=None, gamma=0.99, lam=0.95,
             bootstrap_truncated=True):

@@ -747,6 +747,70 @@ typedef struct sg_replay_sequences {
 int sg_replay_sequence_device(sg_env *env, const sg_replay *ring, const sg_replay_sequence_config *cfg, int64_t n,
                               const int64_t *index_in_dev, const sg_replay_sequences *out, void *hip_stream);
 
+/* Hindsight goal relabelling (Hindsight Experience Replay, Andrychowicz et al. 2017; SB3's HerReplayBuffer) of a batch of the Goal
+ * ids, in place, in one launch: with probability her_ratio a row's goal becomes the position the ship reached k* steps later in the
+ * same episode.  `batch` is what sg_replay_sample_device (with or without index_in: the prioritized path) has just written from
+ * this ring with n_step = 1; no commit may lie between that call and this one (index names transitions relative to the ring's
+ * head).  batch->index and batch->steps are required here.  The goal is the last two observation columns, (goal - position) *
+ * two_over_world; the achieved position is columns 0, 1.  With h, v, B, T, C as above and c = hdr.sample_calls as the header holds
+ * it when the kernel runs (this call does not advance it: the sampler's own tick is what makes a replayed captured pair draw
+ * afresh), for row j:
+ *   u      = index[j];  outside [0, v B): the row is left untouched and status code 8 is set (relabelled[j] is not written)
+ *   steps[j] != 1: the row is left untouched, relabelled[j] = 2
+ *   q, i   = u / B, u mod B;   p_k = (h - v + q + k) mod T
+ *   w      = philox4x32_10(key = seed, counter = (j lo, j hi, c, 12))       -- the engine's Philox, stream tag 12
+ *   relabel iff (uint64) w2 < thr,  thr = floor(her_ratio * 2^32 + 0.5) computed on the host; else untouched, relabelled[j] = 0
+ *   m      = min(horizon - 1, v - 1 - q, the first k with done[p_k, i])     -- the n-step walk's stopping rule: the window
+ *            0 .. m never crosses an episode end or the newest edge
+ *   k*     = umul64hi(w0 | w1 << 32, m + 1) (strategy 0, "future": 0 .. m, the step's own end position included, as SB3's);
+ *            m (strategy 1, "final")
+ *   a      = columns 0, 1 of s' of (p_k*, i): term_obs[term_idx[p_k*, i] mod C] where done[p_k*, i], else ring.obs[p_k*, i]
+ *   x0, x1 = columns 0, 1 of batch.obs[j], batch.next_obs[j];  o = columns D - 2, D - 1 of batch.next_obs[j] as they were
+ *   batch.obs[j, D - 2 + d]      = (a_d - x0_d) * two_over_world            -- float32: one subtract, one multiply (the engine's
+ *   batch.next_obs[j, D - 2 + d] = (a_d - x1_d) * two_over_world               goal_observe)
+ *   the reward, float64, every operation rounded on its own (no fused multiply-add), d = 0, 1:
+ *     vo1_d = (double) o_d * (double) half_world                            -- old goal - x1
+ *     vo0_d = vo1_d + ((double) x1_d - (double) x0_d)                       -- old goal - x0
+ *     vn0_d = (double) a_d - (double) x0_d;   vn1_d = (double) a_d - (double) x1_d
+ *     |v|^2 = v_0 v_0 + v_1 v_1;   |v| = sqrt(|v|^2)
+ *     term(v0, v1) = goal_scale * (|v0| - |v1|) + (|v1|^2 < goal_r2 ? sparse : 0.0)
+ *     batch.reward[j] = (float) (((double) reward[j] - term(vo0, vo1)) + term(vn0, vn1))
+ *   relabelled[j] = 1, offset[j] = k*, goal[j] = a                          -- offset and goal are written only where relabelled
+ * goal_scale (goal_vel_reward_scale * 100) and sparse (goal_sparse_reward) are those of env i's CURRENT reward profile
+ * (sg_set_reward_profiles / sg_set_env_profiles; the handle's own values while profiles are off), goal_r2 the handle's.  The
+ * survival and safety terms do not depend on the goal and ride along inside reward.  terminated, truncated, discount and action
+ * are not touched: crashes and time limits do not depend on the goal.
+ * The old goal is taken from next_obs, not from obs: the engine writes the observation before it resamples a goal that was hit, so
+ * the obs of the step after a hit still names the goal that was hit, while its reward was formed under the new one, which its
+ * next_obs names.  Two properties follow from working on a stored batch: the old term is re-formed from float32 observations,
+ * whereas the engine formed it from the unrounded end position, so reward' differs from what the engine would have returned under
+ * the new goal by about goal_scale * ulp(position) (measured: DESIGN section 34); and a stored reward whose goal distance lies
+ * within that rounding of goal_radius may have its sparse bonus mis-subtracted.  With k* = 0 the new goal columns of next_obs are
+ * exactly 0 and the sparse bonus is always present.
+ * The optional outputs (members of `out`, or a NULL `out`): relabelled uint8 [n], offset int32 [n], goal float32 [n, 2].
+ * One launch; the call allocates nothing, never synchronises and is hipGraph-capturable.  n = 0 enqueues nothing.  Status code 8:
+ * no matching header or v = 0 with n > 0 (nothing is written); an index[j] outside [0, v B).  Refused on the host (SG_ERR_INVALID,
+ * nothing enqueued; besides what every replay call refuses, auto_reset off among it): a null cfg or a wrong struct_size, her_ratio
+ * outside [0, 1] or NaN, horizon outside 1 .. T - 1, a strategy other than 0 and 1, n outside 0 .. 2^31 - 1, a null batch or a
+ * null index, steps, obs, next_obs or reward, a Kepler id (no goal), observation or reward normalization on (the ring then holds
+ * normalized values that cannot be decoded).  tests/her_model.py states all of this in NumPy, bit for bit. */
+typedef struct sg_replay_relabel_config {
+    uint32_t struct_size;  /* sizeof(sg_replay_relabel_config), set by sg_replay_relabel_config_init */
+    uint64_t seed;         /* Philox key of the draws */
+    double her_ratio;      /* share of the rows relabelled, in [0, 1] */
+    int32_t horizon;       /* H: 1 .. T - 1, the steps of the future the new goal is drawn from (1: the step's own end position) */
+    int32_t strategy;      /* 0: future, 1: final */
+} sg_replay_relabel_config;
+/* seed 0, her_ratio 0.8, horizon 1, strategy 0 */
+void sg_replay_relabel_config_init(sg_replay_relabel_config *cfg);
+typedef struct sg_replay_relabel_out {
+    uint8_t *relabelled;  /* [n], may be NULL: 0 left as drawn, 1 relabelled, 2 refused (steps != 1) */
+    int32_t *offset;      /* [n], may be NULL: k*, written where relabelled */
+    float *goal;          /* [n, 2], may be NULL: the new goal position, written where relabelled */
+} sg_replay_relabel_out;
+int sg_replay_relabel_device(sg_env *env, const sg_replay *ring, const sg_replay_relabel_config *cfg, int64_t n,
+                             const sg_replay_batch *batch, const sg_replay_relabel_out *out, void *hip_stream);
+
 /* Prioritized sampling from the replay ring (Schaul et al. 2016, proportional variant) with an exact integer sum tree.  A
  * caller-owned device object next to the ring holds one priority per cell c = p B + i (slot p, env i: by slot, so nothing moves when
  * the ring wraps) as an UNSIGNED FIXED-POINT INTEGER q with frac_bits fractional bits; every sum over them is a 64-bit integer.

@@ -104,6 +104,17 @@ class SgReplaySequences(C.Structure):
                 ("terminal_obs", C.c_void_p), ("index", C.c_void_p), ("extra_in", C.c_void_p * 4), ("extra_out", C.c_void_p * 4)]
 
 
+class SgReplayRelabelConfig(C.Structure):
+    """sg_replay_relabel_config (include/spacegym.h): sg_replay_relabel_config_init fills in seed 0, her_ratio 0.8, horizon 1, strategy 0"""
+    _fields_ = [("struct_size", C.c_uint32), ("seed", C.c_uint64), ("her_ratio", C.c_double), ("horizon", C.c_int32),
+                ("strategy", C.c_int32)]
+
+
+class SgReplayRelabelOut(C.Structure):
+    """sg_replay_relabel_out (include/spacegym.h): the optional outputs of sg_replay_relabel_device"""
+    _fields_ = [("relabelled", C.c_void_p), ("offset", C.c_void_p), ("goal", C.c_void_p)]
+
+
 class SgPriority(C.Structure):
     """sg_priority (include/spacegym.h): the members of the priorities of a replay ring in device memory"""
     _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("frac_bits", C.c_int32), ("reserved", C.c_uint32),
@@ -332,6 +343,9 @@ SYMBOLS = {
     "sg_replay_sequence_config_init": (None, [C.POINTER(SgReplaySequenceConfig)]),
     "sg_replay_sequence_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplaySequenceConfig), C.c_int64, _vp,
                                             C.POINTER(SgReplaySequences), _vp]),
+    "sg_replay_relabel_config_init": (None, [C.POINTER(SgReplayRelabelConfig)]),
+    "sg_replay_relabel_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.POINTER(SgReplayRelabelConfig), C.c_int64, C.POINTER(SgReplayBatch),
+                                           C.POINTER(SgReplayRelabelOut), _vp]),
     "sg_priority_bytes": (C.c_size_t, [_vp, C.c_int32, C.POINTER(C.c_size_t)]),
     "sg_priority_begin_device": (C.c_int, [_vp, C.POINTER(SgPriority), _vp]),
     "sg_priority_commit_device": (C.c_int, [_vp, C.POINTER(SgPriority), C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -140,6 +140,12 @@ class MultiDeviceVectorEnv:
 
     vars().update(dict.fromkeys(NET_METHODS, _no_policy))  # every net method of SpaceGymVectorEnv, in this class's namespace
 
+    def _no_relabel(self, *args, **kwargs):
+        raise NotImplementedError("replay_relabel_torch / replay_sample_her_torch: single-device front end only, not served by "
+                                  "MultiDeviceVectorEnv (one SpaceGymVectorEnv per device keeps a replay ring of its envs)")
+
+    replay_relabel_torch = replay_sample_her_torch = _no_relabel
+
     def step_torch(self, actions):
         """actions: float32 [num_envs, 2] (discrete ids: int32 [num_envs]) on the root device -> (obs, reward, done, truncated)
         for all envs on the root device.  copy=False: the front end's own arrays, two sets that alternate (what a call returns

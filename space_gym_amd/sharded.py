@@ -142,6 +142,12 @@ class ShardedVectorEnv:
 
     vars().update(dict.fromkeys(NET_METHODS, _no_policy))  # every net method of SpaceGymVectorEnv, in this class's namespace
 
+    def _no_relabel(self, *args, **kwargs):
+        raise NotImplementedError("replay_relabel_torch / replay_sample_her_torch: single-device front end only, not served by "
+                                  "ShardedVectorEnv (a rank's SpaceGymVectorEnv keeps a replay ring of its envs)")
+
+    replay_relabel_torch = replay_sample_her_torch = _no_relabel
+
     def _scatter(self, actions, lead=()):
         """rank 0's actions of all envs ([..., num_envs, 2] float32; discrete ids [..., num_envs] int32) -> every rank's block"""
         tail = () if self.discrete else (2,)

@@ -3468,6 +3468,91 @@ class SpaceGymVectorEnv:
         batch["index"], batch["cell"], batch["weight"] = d["index"], d["cell"], d["weight"]
         return batch
 
+    # ------------------------------------------------------------------ hindsight goal relabelling of a replay batch
+    HER_STRATEGIES = {"future": 0, "final": 1}
+
+    def _her_args(self, ring, her_ratio, horizon, strategy, seed):
+        """what both hindsight calls refuse before anything runs: (her_ratio, horizon, strategy code, seed)"""
+        if self.spec["family"] != "goal":
+            raise ValueError(f"replay_relabel_torch: {self.env_id} has no goal to relabel (a Goal id expected)")
+        T = ring.steps
+        her_ratio, seed = float(her_ratio), int(seed)
+        H = T - 1 if horizon is None else int(horizon)
+        if not 0.0 <= her_ratio <= 1.0:
+            raise ValueError(f"her_ratio must be in [0, 1], got {her_ratio}")
+        if not 1 <= H <= T - 1:
+            raise ValueError(f"horizon: 1 .. {T - 1} expected for a ring of {T} slots, got {H}")
+        if not isinstance(strategy, str) or strategy not in self.HER_STRATEGIES:
+            raise ValueError(f"strategy: 'future' or 'final' expected, got {strategy!r}")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed: an unsigned 64-bit integer expected, got {seed}")
+        return her_ratio, H, self.HER_STRATEGIES[strategy], seed
+
+    def replay_relabel_torch(self, ring, batch, her_ratio=0.8, horizon=None, strategy="future", seed=0, out=None):
+        """Hindsight Experience Replay on a batch of a Goal id, in place (sg_replay_relabel_device: one launch; torch's current
+        stream, no host synchronisation, graph-capturable).  batch: the dict replay_sample_torch or
+        replay_sample_prioritized_torch has just returned from this ring with n_step = 1 (index and steps included), no commit in
+        between.  With probability her_ratio a row's goal becomes the position the ship reached k steps later in the same episode:
+        k uniform on 0 .. m ("future"; 0 is the step's own end position, as SB3's) or k = m ("final"), m the last of the next
+        `horizon` steps (default: all the ring holds, steps - 1) before an episode end or the ring's newest edge.  The goal columns
+        of obs and next_obs and the goal term of reward are rewritten (each env's current reward profile); action, terminated,
+        truncated, discount, weight and cell stay as drawn.  Returns `batch` with relabelled (uint8 [n]: 0 as drawn, 1 relabelled,
+        2 refused: steps != 1), offset (int32 [n]: k) and goal (float32 [n, 2]: the new goal position) added; the last two are
+        written where relabelled.  out: a dict of such tensors to write into.  Refused: a Kepler id and auto_reset off
+        (ValueError), observation or reward normalization on (by the native call: NativeError).  tests/her_model.py states the arithmetic."""
+        import torch
+        r = self._replay_arg(ring)
+        her_ratio, H, code, seed = self._her_args(ring, her_ratio, horizon, strategy, seed)
+        if not isinstance(batch, dict) or any(k not in batch for k in ("obs", "next_obs", "reward", "steps", "index")):
+            raise ValueError("batch: a dict with obs, next_obs, reward, steps and index expected (what replay_sample_torch returns)")
+        D = self.obs_dim
+        n = int(batch["index"].shape[0]) if isinstance(batch["index"], torch.Tensor) and batch["index"].dim() == 1 else -1
+        if not 0 <= n <= 2 ** 31 - 1:
+            raise ValueError("batch['index']: a one-dimensional int64 tensor expected")
+        for k, (dtype, shape) in dict(obs=(torch.float32, (n, D)), next_obs=(torch.float32, (n, D)), reward=(torch.float32, (n,)),
+                                      steps=(torch.uint8, (n,)), index=(torch.int64, (n,))).items():
+            self._check_tensor(f"batch['{k}']", batch[k], dtype, shape)
+        spec = dict(relabelled=(torch.uint8, (n,)), offset=(torch.int32, (n,)), goal=(torch.float32, (n, 2)))
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.zeros(shape, dtype=dtype, device=dev) for k, (dtype, shape) in spec.items()}
+        else:
+            for k, (dtype, shape) in spec.items():
+                if k in out:
+                    self._check_tensor(f"out['{k}']", out[k], dtype, shape)
+        cfg = _native.SgReplayRelabelConfig(C.sizeof(_native.SgReplayRelabelConfig), seed, her_ratio, H, code)
+        b = _native.SgReplayBatch(obs=batch["obs"].data_ptr(), reward=batch["reward"].data_ptr(), next_obs=batch["next_obs"].data_ptr(),
+                                  steps=batch["steps"].data_ptr(), index=batch["index"].data_ptr())
+        o = _native.SgReplayRelabelOut(*(out[k].data_ptr() if k in out else None for k in spec))
+        self._ck(self._lib.sg_replay_relabel_device(self._h, C.byref(r), C.byref(cfg), n, C.byref(b), C.byref(o), self._stream()),
+                 "sg_replay_relabel_device")
+        for k in spec:
+            if k in out:
+                batch[k] = out[k]
+        return batch
+
+    def replay_sample_her_torch(self, ring, n, her_ratio=0.8, horizon=None, strategy="future", seed=0, gamma=0.99, prio=None, beta=0.4,
+                                stratified=True, normalize=True, out=None):
+        """A minibatch of n single-step transitions with hindsight goals: replay_sample_torch (prio=None) or
+        replay_sample_prioritized_torch (prio: the ring's ReplayPriority; weight and cell are left as drawn) with n_step = 1, then
+        replay_relabel_torch with the same seed.  A composition of those calls: it ADDS NO NATIVE CODE of its own.  out: a dict to
+        write into, the sampler's members and optionally relabelled, offset, goal."""
+        extra = ("relabelled", "offset", "goal")
+        self._replay_arg(ring)
+        self._her_args(ring, her_ratio, horizon, strategy, seed)  # (refused before the sampler advances the ring's call counter)
+        sample_out = None if out is None else {k: v for k, v in out.items() if k not in extra}
+        if prio is None:
+            batch = self.replay_sample_torch(ring, n, seed=seed, n_step=1, gamma=gamma, out=sample_out)
+        else:
+            batch = self.replay_sample_prioritized_torch(ring, prio, n, seed=seed, beta=beta, stratified=stratified, n_step=1, gamma=gamma,
+                                                         normalize=normalize, out=sample_out)
+        batch = self.replay_relabel_torch(ring, batch, her_ratio=her_ratio, horizon=horizon, strategy=strategy, seed=seed,
+                                          out=None if out is None else {k: out[k] for k in extra if k in out})
+        if out is not None:
+            out.update({k: batch[k] for k in extra if k in batch})
+            return out
+        return batch
+
     def random_actions_torch(self, n_steps, seed=0, first_step=0, out=None):
         """the uniformly random policy generated on the device: [n_steps, B, 2] float32 in (-1, 1) (discrete ids: int32
         [n_steps, B] in 0..5); entry (t, i) depends only on (seed, global env index, first_step + t)."""

@@ -586,6 +586,72 @@ int sg_vtrace_device(sg_env *env, int32_t n_steps, const sg_returns_config *cfg,
                      const float *terminal_value_dense_dev, const sg_value_list *terminal_value_list, float *vs_dev,
                      float *pg_advantage_dev, void *hip_stream);
 
+/* Retrace(lambda) and Q(lambda) targets over replayed sequences: what turns a sampled [L, n] sequence batch (sg_replay_sequence_device)
+ * into multi-step, off-policy-corrected targets for Q(s_t, a_t) -- the action-value counterpart of sg_vtrace_device, for a DQN, an
+ * R2D2-style or a SAC-critic learner (Munos et al. 2016, "Safe and efficient off-policy reinforcement learning").  Device call only;
+ * tests/retrace_model.py is the recurrence and the loss outputs in NumPy, bit for bit; DESIGN section 35 has the kernel.
+ * Unlike sg_vtrace_device it takes the column count n explicitly (1 .. 2^31 - 1, with length * n <= 2^31 - 1): a sequence batch is not
+ * num_envs wide.  All arrays are time-major DEVICE tensors:
+ *   reward          float32 [L, n]   required
+ *   done, truncated uint8   [L, n]   required
+ *   q               float32 [L, n]   required: Q(s_t, a_t) of the net the targets are built from (normally the target net)
+ *   value           float32 [L, n]   required: V_pi(s_t) = E_{a ~ pi} Q(s_t, a) under the target policy
+ *   last_value      float32 [n]      V_pi(s_L); NULL: zeros
+ *   ratio           float32 [L, n]   the caller's per-step trace ratio; NULL: ones.  No exp runs on the device.
+ *   terminal_value  float32 [L, n]   dense; read ONLY where done && truncated (sg_replay_sequence_device leaves terminal_obs unwritten
+ *                                    elsewhere, so nothing else is read); NULL: a truncation bootstraps from 0
+ *   target          float32 [L, n]   output, required
+ *   q_online        float32 [L, n]   optional input: the online net's Q(s_t, a_t)
+ *   weight          float32 [n]      optional input: per-sequence importance weights
+ *   td_error        float32 [L, n]   optional output: q_online - target
+ *   g               float32 [L, n]   optional output: the Huber loss' gradient by q_online (below); flattened, it is the g_taken of
+ *                                    sg_dqn_grad_device / sg_q_grad_device
+ * Per column i, in float64, every operation rounded on its own (no fused multiply-add):
+ *   carry = 0;  v_next = last_value[i] (0 if NULL)
+ *   for t = L - 1 .. 0:
+ *       if done[t, i]:  boot = (truncated[t, i] && bootstrap_truncated && terminal_value) ? terminal_value[t, i] : 0
+ *       else:           boot = v_next + carry
+ *       G  = reward[t, i] + gamma * boot                                -- product rounded, then sum
+ *       target[t, i] = (float) G
+ *       rho = ratio ? ratio[t, i] : 1;   cc = c_bar < rho ? c_bar : rho    -- a NaN ratio stays NaN
+ *       carry  = (lambda * cc) * (G - q[t, i])
+ *       v_next = value[t, i]
+ * which is the Retrace operator with c_t = lambda min(c_bar, ratio_t),
+ *   G_t = r_t + gamma [V_pi(s_{t+1}) + c_{t+1} (G_{t+1} - Q(s_{t+1}, a_{t+1}))],
+ * cut at episode ends and bootstrapped from last_value at the sequence's end.  ratio and c_bar pick the estimator; the kernel has no mode:
+ *   Retrace(lambda)        ratio = pi / mu, c_bar = 1          tree backup(lambda)    ratio = pi(a_t | s_t)
+ *   Peng's Q(lambda)       ratio = NULL                        Watkins' Q(lambda)     ratio = [a_t greedy]
+ *   importance sampling    ratio = pi / mu, c_bar = inf        one-step TD            lambda = 0
+ * Where td_error or g is given, in float32 with sg_dqn_td_grad_device's arithmetic:
+ *   td = q_online[t, i] - target[t, i];  c = min(max(td, -huber_delta), huber_delta);  w = weight ? weight[i] : 1
+ *   td_error[t, i] = td;  g[t, i] = (w * c) / (float)(L * n)              -- the product rounded, then the quotient
+ * No statistics are written: the reductions stay with the caller or the TD calls.
+ *   discounts  optional DEVICE float32 [2] of (gamma, lambda), read by the kernel at every launch -- a captured graph anneals both by
+ *              writing the tensor.  ITS VALUES ARE NOT CHECKED.  The two floats are widened to float64 (exact); the recurrence has no
+ *              gamma * lambda product, so the tensor form gives the bits of the scalar form at gamma = (double)(float) g, lambda
+ *              likewise.  When it is given, cfg's gamma and lambda are not read.
+ * One launch on the caller's stream: no workspace, no atomics, no LDS, nothing allocated, no synchronisation, hipGraph-capturable.  Every
+ * load and store is one element per lane, so an odd n and views at odd offsets work.
+ * Refused on the host (SG_ERR_INVALID, nothing enqueued): a null cfg, a wrong struct_size or a non-zero reserved; length < 1, n < 1,
+ * length * n > 2^31 - 1; a null reward, done, truncated, q, value or target; with a null discounts, gamma or lambda outside [0, 1] or NaN;
+ * c_bar or huber_delta <= 0 or NaN (+inf allowed: no clipping, the squared loss); td_error or g without q_online; weight without g. */
+typedef struct sg_retrace_config {
+    uint32_t struct_size;         /* sizeof(sg_retrace_config), set by sg_retrace_config_init */
+    double gamma;                 /* discount, in [0, 1]; not read when discounts is given */
+    double lambda;                /* the trace's lambda, in [0, 1]; not read when discounts is given */
+    double c_bar;                 /* clips the ratio of the trace; > 0, +inf allowed */
+    int32_t bootstrap_truncated;  /* as sg_gae_config's */
+    float huber_delta;            /* the loss outputs' Huber threshold; > 0, +inf: the squared loss */
+    const float *discounts;       /* optional DEVICE float32 [2]: (gamma, lambda), read at every launch */
+    int32_t reserved;             /* 0 */
+} sg_retrace_config;
+/* gamma 0.99, lambda 1.0, c_bar 1.0, bootstrap_truncated 1, huber_delta +inf and a null discounts */
+void sg_retrace_config_init(sg_retrace_config *cfg);
+int sg_retrace_device(sg_env *env, int32_t length, int32_t n, const sg_retrace_config *cfg, const float *reward_dev, const uint8_t *done_dev,
+                      const uint8_t *truncated_dev, const float *q_dev, const float *value_dev, const float *last_value_dev,
+                      const float *ratio_dev, const float *terminal_value_dev, float *target_dev, const float *q_online_dev,
+                      const float *weight_dev, float *td_error_dev, float *g_dev, void *hip_stream);
+
 /* Replay ring with uniform n-step sampling -- what an off-policy learner (SAC, TD3: the learners the reference's README names) keeps
  * around the step: the last transitions (s, a, r, s', terminated), where s' of a finished step is the LAST observation of the episode
  * that ended (not the first one of the next episode, which auto-reset put into obs[t]) and a truncated step still bootstraps (SB3
@@ -714,7 +780,8 @@ int sg_replay_sample_device(sg_env *env, const sg_replay *ring, const sg_replay_
  *   extra_out[e][k, j] = extra_in[e][p_k, i]     -- e < n_extra <= 4
  *   index[j]           = u
  * Outputs: obs [L + 1, n, D], action [L, n, 2] (discrete ids: int32 [L, n]), reward, done, trunc [L, n]; with n = num_envs they go
- * straight into sg_gae_device / sg_gae_groups_device / sg_vtrace_device, with terminal_value = V(terminal_obs) in the dense form.
+ * straight into sg_gae_device / sg_gae_groups_device / sg_vtrace_device, with terminal_value = V(terminal_obs) in the dense form; with
+ * any n into sg_retrace_device (Retrace, Q(lambda)).
  * terminal_obs [L, n, D], index [n] and the extras may be NULL; the learner reads terminal_obs only where done.  extra_in[e] are
  * caller-owned float32 [T, B] device arrays in the ring's slot layout (a closed-loop rollout's logp / value buffers are slices of
  * them: they are how the behaviour log-prob reaches V-trace); the ring does not own them and commits do not touch them.

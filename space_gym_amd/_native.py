@@ -74,6 +74,13 @@ class SgReturnsConfig(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SgRetraceConfig(C.Structure):
+    """sg_retrace_config (include/spacegym.h): sg_retrace_config_init fills in gamma 0.99, lambda 1.0, c_bar 1.0, bootstrap_truncated 1,
+    huber_delta +inf and a null discounts"""
+    _fields_ = [("struct_size", C.c_uint32), ("gamma", C.c_double), ("lambda_", C.c_double), ("c_bar", C.c_double),
+                ("bootstrap_truncated", C.c_int32), ("huber_delta", C.c_float), ("discounts", C.c_void_p), ("reserved", C.c_int32)]
+
+
 class SgReplay(C.Structure):
     """sg_replay (include/spacegym.h): the members of a replay ring in device memory"""
     _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_int32), ("term_capacity", C.c_uint32), ("reserved", C.c_uint32),
@@ -334,6 +341,9 @@ SYMBOLS = {
                                        _vp]),
     "sg_vtrace_device": (C.c_int, [_vp, C.c_int32, C.POINTER(SgReturnsConfig), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(SgValueList), _vp, _vp,
                                    _vp]),
+    "sg_retrace_config_init": (None, [C.POINTER(SgRetraceConfig)]),
+    "sg_retrace_device": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(SgRetraceConfig), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
     "sg_replay_bytes": (C.c_size_t, [_vp, C.c_int32, C.c_uint32, C.POINTER(C.c_size_t)]),
     "sg_replay_begin_device": (C.c_int, [_vp, C.POINTER(SgReplay), _vp, _vp]),
     "sg_replay_commit_device": (C.c_int, [_vp, C.POINTER(SgReplay), C.c_int32, C.c_int32, C.c_int32, C.POINTER(SgTerminalList), _vp, _vp]),

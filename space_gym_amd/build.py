@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libspacegym_hip.so")
 SOURCES = ["sg_engine.hip"]
-HEADERS = ["sg_device.hpp", "sg_host_config.hpp", "sg_config.h", "sg_goal_pair_rollout.inc", "sg_kepler_pair_rollout.inc", "sg_gae.inc", "sg_returns.inc", "sg_replay.inc", "sg_sequence.inc", "sg_her.inc", "sg_priority.inc", "sg_policy.inc", "sg_policy_grad.inc", "sg_qnet.inc", "sg_squashed.inc", "sg_q_td.inc", "sg_q_actor.inc", "sg_dqn.inc", "sg_dqn_td.inc", "sg_population.inc", "sg_ppo.inc", "sg_adam.inc", "sg_pbt.inc", "sg_minibatch.inc", os.path.join(ROOT, "include", "spacegym.h")]
+HEADERS = ["sg_device.hpp", "sg_host_config.hpp", "sg_config.h", "sg_goal_pair_rollout.inc", "sg_kepler_pair_rollout.inc", "sg_gae.inc", "sg_returns.inc", "sg_retrace.inc", "sg_replay.inc", "sg_sequence.inc", "sg_her.inc", "sg_priority.inc", "sg_policy.inc", "sg_policy_grad.inc", "sg_qnet.inc", "sg_squashed.inc", "sg_q_td.inc", "sg_q_actor.inc", "sg_dqn.inc", "sg_dqn_td.inc", "sg_population.inc", "sg_ppo.inc", "sg_adam.inc", "sg_pbt.inc", "sg_minibatch.inc", os.path.join(ROOT, "include", "spacegym.h")]
 ARCH = "gfx950"
 
 

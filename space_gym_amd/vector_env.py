@@ -327,7 +327,7 @@ NET_METHODS = ("policy_torch", "policy_act_torch", "rollout_policy_torch", "poli
                "population_grad_torch", "population_ppo_grad_torch", "adam_torch", "adam_step_torch", "adam_exploit_torch", "pbt_fitness_torch",
                "pbt_fitness_update_torch", "pbt_fitness_clear_torch", "pbt_select_torch", "pbt_explore_torch", "minibatch_index_torch",
                "ppo_update_torch", "dqn_td_grad_torch", "dqn_update_torch", "q_td_grad_torch",
-               "q_update_torch", "q_actor_grad_torch", "q_actor_update_torch")
+               "q_update_torch", "q_actor_grad_torch", "q_actor_update_torch", "retrace_torch", "dqn_retrace_grad_torch")
 
 
 class SpaceGymVectorEnv:
@@ -1369,6 +1369,87 @@ class SpaceGymVectorEnv:
                                             ptr(terminal_value), C.byref(vl) if vl is not None else None, ptr(out["vs"]),
                                             ptr(out["pg_advantage"]), self._stream()), "sg_vtrace_device")
         return out["vs"], out["pg_advantage"]
+
+    # ------------------------------------------------------------------ Retrace(lambda) / Q(lambda) targets over replayed sequences
+    _RETRACE_LOSS_KEYS = ("q_online", "weight", "huber_delta", "td_error", "g")
+
+    def retrace_torch(self, reward, done, trunc, q, value, last_value=None, ratio=None, terminal_value=None, gamma=0.99, lam=1.0, c_bar=1.0,
+                      discounts=None, bootstrap_truncated=True, out=None, loss=None):
+        """Multi-step off-policy-corrected targets for Q(s_t, a_t) over a time-major sequence batch [L, n] -- what
+        replay_sample_sequences_torch returns, any n (sg_retrace_device; Munos et al. 2016): one launch on torch's current stream, no
+        host synchronisation, graph-capturable.  q float32 [L, n]: Q(s_t, a_t) of the net the targets are built from (normally the
+        target net); value float32 [L, n]: V_pi(s_t) = E_{a ~ pi} Q(s_t, a) under the target policy; last_value float32 [n]: V_pi(s_L)
+        (None: zeros).  Per column, backwards in float64:
+            G_t = r_t + gamma * (done_t ? (trunc_t ? terminal_value_t : 0) : value_{t+1} + c_{t+1} (G_{t+1} - q_{t+1})),
+            c_t = lam * min(c_bar, ratio_t)
+        and target = float32(G).  ratio float32 [L, n] is the caller's (no exp runs on the device) and picks the estimator: pi / mu with
+        c_bar = 1 is Retrace(lambda); pi(a_t | s_t) tree backup; None (all ones) Peng's Q(lambda); [a_t greedy] Watkins' Q(lambda);
+        pi / mu with c_bar = float("inf") plain importance sampling; lam = 0 one-step TD.  terminal_value float32 [L, n] is read only
+        where done and trunc are both set (None, or bootstrap_truncated=False: a truncation bootstraps from 0).  The discounts are the
+        scalars gamma / lam in [0, 1], or -- discounts given -- a float32 device tensor [2] of (gamma, lam) that the kernel reads at
+        every launch or graph replay (its values are not checked; gamma and lam are then not read).  c_bar > 0.  out: the float32
+        [L, n] target to fill (allocated when None).
+        loss: None, or dict(q_online=float32 [L, n], weight=None or float32 [n], huber_delta=inf, td_error=None, g=None): the same launch
+        also writes td_error = q_online - target and g = (weight * clip(td_error, -huber_delta, huber_delta)) / (L * n), the Huber
+        loss' gradient by q_online -- flattened, the g_taken of dqn_grad_torch / q_grad_torch (td_error, g: float32 [L, n] tensors to
+        fill, allocated when None).  Returns target, or with loss (target, td_error, g).  tests/retrace_model.py states the arithmetic."""
+        import torch
+        c_bar = float(c_bar)
+        if not c_bar > 0.0:
+            raise ValueError(f"c_bar must be > 0, got {c_bar}")
+        if discounts is None:
+            checked = self._gae_config(gamma, lam, bootstrap_truncated)  # (gamma and lam in [0, 1])
+            gamma, lam = checked.gamma, checked.lambda_
+        else:
+            gamma, lam = 0.99, 1.0  # (not read)
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+            raise ValueError("reward: expected a CUDA tensor of shape (L, n)")
+        L, n = int(reward.shape[0]), int(reward.shape[1])
+        if L < 1 or n < 1:
+            raise ValueError("reward: expected at least one step and one column")
+        if L * n > 2 ** 31 - 1:
+            raise ValueError(f"reward: L * n = {L * n}: at most 2^31 - 1 (elements are addressed by 32 bits)")
+        self._check_tensor("reward", reward, torch.float32, (L, n))
+        self._check_tensor("done", done, torch.uint8, (L, n))
+        self._check_tensor("trunc", trunc, torch.uint8, (L, n))
+        if q is None:
+            raise ValueError("q: Retrace needs Q(s_t, a_t) of the actions taken")
+        if value is None:
+            raise ValueError("value: Retrace needs V_pi(s_t) of the sequence's observations")
+        for name, t, shape in (("q", q, (L, n)), ("value", value, (L, n)), ("last_value", last_value, (n,)), ("ratio", ratio, (L, n)),
+                               ("terminal_value", terminal_value, (L, n)), ("discounts", discounts, (2,))):
+            if t is not None:
+                self._check_tensor(name, t, torch.float32, shape)
+        q_online = weight = td_error = g = None
+        huber_delta = float("inf")
+        if loss is not None:
+            if not isinstance(loss, dict) or set(loss) - set(self._RETRACE_LOSS_KEYS):
+                raise ValueError(f"loss: expected a dict with keys among {self._RETRACE_LOSS_KEYS}")
+            q_online, weight = loss.get("q_online"), loss.get("weight")
+            if q_online is None:
+                raise ValueError("loss['q_online']: missing")
+            self._check_tensor("loss['q_online']", q_online, torch.float32, (L, n))
+            if weight is not None:
+                self._check_tensor("loss['weight']", weight, torch.float32, (n,))
+            huber_delta = float(loss.get("huber_delta", float("inf")))
+            if not huber_delta > 0.0:
+                raise ValueError(f"loss['huber_delta'] must be > 0, got {huber_delta}")
+            for k in ("td_error", "g"):
+                if loss.get(k) is not None:
+                    self._check_tensor(f"loss['{k}']", loss[k], torch.float32, (L, n))
+        if out is None:
+            out = torch.empty((L, n), dtype=torch.float32, device=reward.device)
+        else:
+            self._check_tensor("out", out, torch.float32, (L, n))
+        if loss is not None:
+            td_error, g = (loss.get(k) if loss.get(k) is not None else torch.empty((L, n), dtype=torch.float32, device=reward.device)
+                           for k in ("td_error", "g"))
+        cfg = _native.SgRetraceConfig(C.sizeof(_native.SgRetraceConfig), gamma, lam, c_bar, int(bool(bootstrap_truncated)), huber_delta,
+                                      discounts.data_ptr() if discounts is not None else None, 0)
+        self._ck(self._lib.sg_retrace_device(self._h, L, n, C.byref(cfg), _ptr(reward), _ptr(done), _ptr(trunc), _ptr(q), _ptr(value),
+                                             _ptr(last_value), _ptr(ratio), _ptr(terminal_value), _ptr(out), _ptr(q_online), _ptr(weight),
+                                             _ptr(td_error), _ptr(g), self._stream()), "sg_retrace_device")
+        return out if loss is None else (out, td_error, g)
 
     # ------------------------------------------------------------------ what the net handles and their methods share
     def _mlp_layers(self, name, layers, fan_in, out, mlp, keep, members=None):
@@ -2698,6 +2779,66 @@ class SpaceGymVectorEnv:
             huber(env.dqn_evaluate_torch(online, obs, action)[1], target).mean().backward()"""
         self._dqn_rows(dqn, "dqn_evaluate_torch", obs, action)
         return _net_function("DqnEvaluate", _dqn_forward, _dqn_backward).apply(self, dqn, obs, action, *dqn.tensors)
+
+    # ------------------------------------------------------------------ a DQN update on Retrace(lambda) / Q(lambda) targets of sequences
+    retrace_traces = ("retrace", "tree_backup", "peng", "watkins", "is")
+
+    def dqn_retrace_grad_torch(self, online, target_net, seq, mu=None, trace="retrace", epsilon=0.0, gamma=0.99, lam=1.0, huber_delta=1.0,
+                               weight=None):
+        """The online net's gradients of the Huber loss against Retrace(lambda) / Q(lambda) targets of a sequence batch, without
+        autograd: a composition of dqn_evaluate_raw_torch, retrace_torch and dqn_grad_torch with no native code of its own, no host
+        synchronisation, graph-capturable after one warm-up call.  online, target_net: dqn_torch handles of one architecture.  seq:
+        the dict replay_sample_sequences_torch returns (obs [L + 1, n, D], action int32 [L, n], reward, done, trunc, terminal_obs
+        [L, n, D]).  terminal_obs MUST BE A PREFILLED FINITE BUFFER: the sampler writes it only where done, and the target net is
+        evaluated on all of it (the sampler's own allocation is zeros; retrace_torch then reads the values only where done and trunc).
+        The target policy pi is greedy (epsilon 0.0) or epsilon-greedy in the target net, epsilon a float in [0, 1]:
+            pi(a | s) = (1 - epsilon) [a == argmax] + epsilon / 6,    value = (1 - epsilon) q_max + (epsilon / 6) sum_j q_all[j]
+        trace picks the ratio of retrace_torch: "retrace" pi / mu with c_bar 1; "tree_backup" pi; "peng" none; "watkins"
+        [a == argmax]; "is" pi / mu with c_bar inf.  mu float32 [L, n]: the behaviour policy's probability of the action taken,
+        gathered by the sampler's columns= as a rollout's logp is; needed by "retrace" and "is".  weight: float32 [n] per-sequence
+        importance weights.  Returns (grads, rows): grads is dqn_grad_torch's dict, accepted by adam_step_torch as is; rows is
+        dict(target, td_error, g) of float32 [L, n]."""
+        import torch
+        self._dqn_handle(online, "dqn_retrace_grad_torch")
+        self._dqn_handle(target_net, "dqn_retrace_grad_torch")
+        if trace not in self.retrace_traces:
+            raise ValueError(f"trace: expected one of {self.retrace_traces}, got {trace!r}")
+        eps, eps_dev = self._dqn_epsilon(epsilon)
+        if eps_dev is not None:
+            raise ValueError("epsilon: expected a float in [0, 1] (the target policy has one epsilon)")
+        if not isinstance(seq, dict) or not isinstance(seq.get("obs"), torch.Tensor) or seq["obs"].dim() != 3 or int(seq["obs"].shape[0]) < 2:
+            raise ValueError("seq: expected the dict replay_sample_sequences_torch returns (obs [L + 1, n, D], action, reward, done, trunc, "
+                             "terminal_obs)")
+        L, n, D = int(seq["obs"].shape[0]) - 1, int(seq["obs"].shape[1]), self.obs_dim
+        for k, dtype, shape in (("obs", torch.float32, (L + 1, n, D)), ("action", torch.int32, (L, n)), ("terminal_obs", torch.float32, (L, n, D))):
+            if seq.get(k) is None:
+                raise ValueError(f"seq['{k}']: missing")
+            self._check_tensor(f"seq['{k}']", seq[k], dtype, shape)
+        needs_mu = trace in ("retrace", "is")
+        if needs_mu and mu is None:
+            raise ValueError(f"mu: trace {trace!r} needs the behaviour policy's probability of the action taken, float32 [L, n]")
+        if mu is not None:
+            self._check_tensor("mu", mu, torch.float32, (L, n))
+        obs, last_obs = seq["obs"][:L].reshape(L * n, D), seq["obs"][L]
+        action = seq["action"].reshape(L * n)
+
+        def value_of(q_all, q_max):
+            return q_max if eps == 0.0 else (1.0 - eps) * q_max + (eps / 6.0) * q_all.sum(dim=1)
+        q_all, q, q_max, argmax = self.dqn_evaluate_raw_torch(target_net, obs, action)
+        value = value_of(q_all, q_max).reshape(L, n)
+        last_all, _, last_max, _ = self.dqn_evaluate_raw_torch(target_net, last_obs)
+        term_all, _, term_max, _ = self.dqn_evaluate_raw_torch(target_net, seq["terminal_obs"].reshape(L * n, D))
+        q_online = self.dqn_evaluate_raw_torch(online, obs, action)[1]
+        greedy = (action == argmax).to(torch.float32).reshape(L, n)
+        pi = greedy if eps == 0.0 else (1.0 - eps) * greedy + eps / 6.0
+        ratio = {"retrace": lambda: pi / mu, "is": lambda: pi / mu, "tree_backup": lambda: pi, "watkins": lambda: greedy,
+                 "peng": lambda: None}[trace]()
+        rows = self.retrace_torch(seq["reward"], seq["done"], seq["trunc"], q.reshape(L, n), value, last_value=value_of(last_all, last_max),
+                                  ratio=ratio, terminal_value=value_of(term_all, term_max).reshape(L, n), gamma=gamma, lam=lam,
+                                  c_bar=float("inf") if trace == "is" else 1.0,
+                                  loss=dict(q_online=q_online.reshape(L, n), weight=weight, huber_delta=huber_delta))
+        grads = self.dqn_grad_torch(online, obs, action, g_taken=rows[2].reshape(L * n))
+        return grads, dict(target=rows[0], td_error=rows[1], g=rows[2])
 
     # ------------------------------------------------------------------ the Double-DQN TD update: target, Huber loss, statistics and gradients
     dqn_td_stats_names = ("loss", "td_abs_mean", "td_abs_max", "q_mean", "target_mean", "clip_fraction", "weight_mean", "bad_rows")
